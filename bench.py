@@ -11,6 +11,12 @@ per GPU, RCCL) every rank runs its own envs (seed 42 + env id) and the
 trajectory buffers are all-gathered at the end of each episode.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up the headline workload,
+warms up, times the N steps and prints the line.  `--full` adds everything
+else: the other lines (--only), the run kernel's own timing and the slice
+timeline behind the rooflines, and the CPU comparator.  `--dump-outputs DIR`
+writes what the last timed step of the headline computed as DIR/<name>.npy.
 """
 
 import argparse
@@ -39,6 +45,7 @@ VALU_PEAK_WAVE_INSTS = SIMD_CLOCKS_PER_S / VALU_CYCLES
 F32_VECTOR_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: F32 row (= vector peak)
 BYTES_PER_PARTICLE_SUBSTEP = 40
 PPO_MAC_PER_SAMPLE = 2944        # DESIGN.md section 6 "PPO update" (3-128-(4+1) MLP)
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all arrays of one run together
 # the lines one bench.py run can measure (--only): see main()
 LINES = ("head", "batched", "c2", "c4", "c5", "c3train", "dims3", "dense2d")
 
@@ -105,7 +112,21 @@ def parse_args():
                          "update) run through it as at N GPUs (rollout.force_collectives)")
     ap.add_argument("--stub", action="store_true",
                     help="CPU plumbing test: no GPU, gloo, synthetic trajectories")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline's timed steps: the other lines (--only), the run "
+                         "kernel's own timing and slice timeline (rooflines), the PPO update's "
+                         "roofline and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline, write what its last step "
+                         "computed (the trajectory entries a caller receives and the engine "
+                         "state) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full and args.only not in ("all", "head"):
+        ap.error("--only selects lines of the --full run: add --full")
+    only = [x.strip() for x in args.only.split(",")]
+    if args.dump_outputs and (args.stub or (only != ["all"] and "head" not in only)):
+        ap.error("--dump-outputs writes the headline's outputs: it needs the 'head' line on a GPU")
+    return args
 
 
 def build_workload(args, env_seed, device):
@@ -699,7 +720,7 @@ def cpu_baseline_all_cores(args):
     }
 
 
-def capture_episode(eng, ff, agent, T):
+def capture_episode(eng, ff, agent, T, keep_slice_outputs=False):
     """Two eager warm-up slices on a side stream, then the graphs the bench
     replays: one per slice (for step counts that are not a multiple of T) and
     one per episode, whose T slices write T distinct trajectory tensors, so
@@ -722,6 +743,10 @@ def capture_episode(eng, ff, agent, T):
     # queries: hipErrorStreamCaptureUnsupported, seen on a world-1 RCCL group)
     with torch.cuda.graph(slice_graph, capture_error_mode="thread_local"):
         eng.integrate(1, ff)
+    if keep_slice_outputs:
+        # the slice graph's output tensors (a replay writes the slice's
+        # trajectory entry here), for --dump-outputs
+        slice_graph.trajectory = agent.trajectory
     agent.reset_trajectory()
     episode_graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(episode_graph, pool=slice_graph.pool(),
@@ -733,11 +758,14 @@ def capture_episode(eng, ff, agent, T):
 
 
 def measure(args, E, rank, world, device, builder=None, colloids=None, line="head",
-            train=False):
+            train=False, dump_dir=None):
     """Build, capture and time one workload of E envs per GPU; returns the
     timing and roofline numbers (all ranks).  train: each episode is also
     followed by the agent's PPO update (ProximalPolicyLoss.compute_loss,
-    proximal_policy_loss.py:140-170) inside the timed region."""
+    proximal_policy_loss.py:140-170) inside the timed region.  dump_dir:
+    write the last timed step's outputs there (dump_outputs).  The run
+    kernel's own timing and the update's roofline take runs of their own
+    after the timed region: with args.full only."""
     import torch
     import torch.distributed as dist
 
@@ -767,12 +795,14 @@ def measure(args, E, rank, world, device, builder=None, colloids=None, line="hea
     T = args.episode_length
     slice_graph = episode_graph = None
     if not args.no_graph:
-        slice_graph, episode_graph, _ = capture_episode(eng, ff, agent, T)
+        slice_graph, episode_graph, _ = capture_episode(eng, ff, agent, T,
+                                                        keep_slice_outputs=dump_dir is not None)
     else:
         agent.reset_trajectory()
 
     gstats = []
     n_updates = [0]
+    last = [None]  # the trajectory that holds the newest step's entries (dump_outputs)
 
     def episode_end(timed):
         """After an episode: the update (train) and the trajectory gather.
@@ -803,13 +833,16 @@ def measure(args, E, rank, world, device, builder=None, colloids=None, line="hea
             if episode_graph is not None and n_steps - k >= T:
                 episode_graph.replay()
                 k += T
+                last[0] = agent.trajectory
                 episode_end(timed)
             elif slice_graph is not None:
                 slice_graph.replay()
                 k += 1
+                last[0] = getattr(slice_graph, "trajectory", None)
             else:
                 one_slice()
                 k += 1
+                last[0] = agent.trajectory
                 if len(agent.trajectory.actions) >= T:
                     episode_end(timed)
                     agent.reset_trajectory()
@@ -846,9 +879,16 @@ def measure(args, E, rank, world, device, builder=None, colloids=None, line="hea
                 "re-runs: windows the exact check sent to the global path",
     }
 
+    if dump_dir is not None:
+        dump_outputs(dump_dir, rank, eng, last[0])
     eng.drain_trajectory(block=True)
     traj_written = eng.h5_time_steps_written + len(eng.traj_holder["Times"])
-    kernel_ms, kernel, timing_note, timed_launches, timeline = time_run_kernel(eng, ff, agent, T)
+    if args.full:
+        kernel_ms, kernel, timing_note, timed_launches, timeline = time_run_kernel(eng, ff, agent,
+                                                                                   T)
+    else:
+        kernel_ms, kernel, timed_launches, timeline = None, None, 0, {}
+        timing_note = "not timed: the run kernel's own timing takes a run of its own (--full)"
     N = args.colloids
     sub = eng.params.steps_per_slice
     out = dict(timing)
@@ -872,13 +912,43 @@ def measure(args, E, rank, world, device, builder=None, colloids=None, line="hea
     valu = out["roofline"].get("valu")
     if valu:
         valu["lane_insts_per_colloid_substep"] = valu["insts_per_launch"] * 64 / (N * sub * E)
-    if train:
+    if train and args.full:
         traj = agent.trajectory  # the episode graph's tensors (eager: the last episode's)
         if len(traj.actions) > 0:
             out["roofline_update"] = time_ppo_grads(agent, traj, line, args.bd_reps)
     del eng, ff, agent, slice_graph, episode_graph
     torch.cuda.synchronize()
     return out
+
+
+def dump_outputs(dump_dir, rank, eng, traj):
+    """--dump-outputs: what the timed path computed in its last step, one
+    DIR/<name>.npy each -- the step's trajectory entries as the agent hands
+    them to its caller (features, log_probs and rewards float32, the action
+    indices as float64) and the engine's exact state after it
+    (get_raw_state: fixed-point positions q, periodic images img, angles ang,
+    integers that float64 holds exactly).  Rank r > 0 prefixes rank<r>_."""
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(dump_dir, exist_ok=True)
+    out = {f"state_{k}": v.astype(np.float64) for k, v in eng.get_raw_state().items()}
+    for name in ("features", "actions", "log_probs", "rewards"):
+        entries = getattr(traj, name, None) if traj is not None else None
+        if entries:
+            t = entries[-1].detach()
+            out[name] = t.to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64
+                             else torch.float64).cpu().numpy()
+    prefix = f"rank{rank}_" if rank else ""
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:  # many envs: the same seeded sample of every array's elements
+        keep = 0.99 * DUMP_MAX_BYTES / total
+        for name, arr in out.items():
+            flat = arr.reshape(-1)
+            idx = np.random.default_rng(0).choice(flat.size, int(flat.size * keep), replace=False)
+            out[name] = flat[np.sort(idx)]
+    for name, arr in out.items():
+        np.save(os.path.join(dump_dir, f"{prefix}{name}.npy"), arr)
 
 
 def launch_ranks(args) -> int:
@@ -989,7 +1059,8 @@ def run_lines(args, lines, rank, world, device):
     """Measure the selected lines; returns {line: record}."""
     res = {}
     if "head" in lines:
-        res["head"] = measure(args, args.envs_per_gpu, rank, world, device, line="head")
+        res["head"] = measure(args, args.envs_per_gpu, rank, world, device, line="head",
+                              dump_dir=args.dump_outputs)
     if "batched" in lines and args.batched_envs > 0:
         r = measure(args, args.batched_envs, rank, world, device, line="batched")
         res["batched"] = _sub_line(r, f"{args.batched_envs} envs x {args.colloids} colloids per "
@@ -1042,7 +1113,10 @@ def run_lines(args, lines, rank, world, device):
 
 def main():
     args = parse_args()
-    lines = LINES if args.only == "all" else tuple(x.strip() for x in args.only.split(","))
+    if not args.full:
+        lines = ("head",)  # a plain run: the headline's timed steps and nothing else
+    else:
+        lines = LINES if args.only == "all" else tuple(x.strip() for x in args.only.split(","))
     bad = [x for x in lines if x not in LINES]
     if bad:
         print(f"bench.py: unknown line(s) {bad}; choose from {LINES}", file=sys.stderr)
@@ -1139,7 +1213,7 @@ def main():
     for k in LINES:
         if k in res:
             line[k] = res[k]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
         line["cpu_baseline"] = cpu_baseline(args)
         if args.cpu_all_core_slices > 0:
             line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args)

@@ -20,7 +20,7 @@ for line in $lines; do
   run() {  # run <subdir> <rocprofv3 options...>
     local sub=$1; shift
     timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$out/$sub" -o run -- \
-      python3 bench.py --only "$line" --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/${sub}_bench.log" 2>&1
+      python3 bench.py --full --only "$line" --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/${sub}_bench.log" 2>&1
   }
   BENCH_ARGS=("$@")
   passes=${PASSES:-"trace fetch write valu"}

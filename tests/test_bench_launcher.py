@@ -39,6 +39,15 @@ def test_launcher_yields_n_ranks_gloo():
     assert line["gather"]["per_run"] == 2
 
 
+def test_other_lines_need_full():
+    """A plain run measures the headline alone: selecting other lines without
+    --full is an error, not a silently shorter run."""
+    r = _bench(["--gpus", "1", "--only", "c2"])
+    assert r.returncode == 2
+    assert "--full" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
 def test_launcher_rejects_world_mismatch():
     r = _bench(["--gpus", "1", "--stub"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode == 2

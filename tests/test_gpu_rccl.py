@@ -155,7 +155,7 @@ def test_bench_c3train_through_a_world1_rccl_group():
     updated by rollout.replicated_update, as at N GPUs."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, "bench.py", "--only", "c3train", "--force-collective",
+    cmd = [sys.executable, "bench.py", "--full", "--only", "c3train", "--force-collective",
            "--train-episodes", "2", "--warmup", "40", "--no-cpu-baseline", "--dims3", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

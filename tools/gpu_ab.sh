@@ -12,7 +12,7 @@ for v in "$@"; do
   [ "$v" != prod ] && lib=$PWD/tools/_variants/lib_${v}.so
   echo "== $v"
   SWARMRL_AMD_LIB=$lib timeout -k 10 150 python3 tools/run_kernel_time.py 1 64 || exit 1
-  SWARMRL_AMD_LIB=$lib timeout -k 10 200 python3 bench.py --only ${LINES:-head,batched} --no-cpu-baseline \
+  SWARMRL_AMD_LIB=$lib timeout -k 10 200 python3 bench.py --full --only ${LINES:-head,batched} --no-cpu-baseline \
     > "$out/bench_$v.json" 2> "$out/bench_$v.err" || exit 1
   python3 -c "import json;d=json.load(open('$out/bench_$v.json'));print({k:(v['value']/1e6 if isinstance(v,dict) and 'value' in v else None) for k,v in d.items() if isinstance(v,dict) and 'value' in v}, 'head', d['value']/1e6)"
 done

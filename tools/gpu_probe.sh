@@ -27,7 +27,7 @@ if [ -n "$EXTRA" ]; then  # one more command (e.g. a rocprofv3 run of a tool), 3
 fi
 prof() {  # prof <dir> <name>
   (cd "$1" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-     -d "$out/prof_$2" -o run -- python3 bench.py --only "$PROF_LINE" --no-cpu-baseline \
+     -d "$out/prof_$2" -o run -- python3 bench.py --full --only "$PROF_LINE" --no-cpu-baseline \
      > "$out/prof_$2.log" 2>&1)
 }
 if [ -n "$PROF_LINE" ]; then

@@ -18,7 +18,7 @@ rc=$?
 echo "tests rc=$rc" >> "$out/gpu_tests.txt"
 # a test failure (1) is not a GPU fault; anything else ends the call here
 if [ $rc -le 1 ] && [ -z "$NO_BENCH" ]; then
-  timeout -k 10 500 python bench.py > "$out/bench.json" 2> "$out/bench.err"
+  timeout -k 10 500 python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
   echo "bench rc=$?" >> "$out/gpu_tests.txt"
 fi
 exit $rc

@@ -17,7 +17,7 @@ SCHEDS = {
 
 CHILD = r"""
 import sys, json
-sys.argv = ["bench.py", "--only", LINE, "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--only", LINE, "--no-cpu-baseline"]
 sys.path.insert(0, ".")
 import bench
 attrs = json.loads(ATTRS)
