@@ -490,6 +490,31 @@ int swarm_engine_policy_mlp_sample(swarm_engine_t *e, const float *obs, int32_t 
                                    float *out_f, float *out_t, float *out_logits,
                                    void *stream);
 
+/* The whole rollout policy of FlaxModel.compute_action
+ * (networks/flax_network.py:153-195) for a deep actor-critic MLP with
+ * n_hidden = 2 or 3 hidden ReLU layers (the three-layer network of
+ * CI/unit_tests/force_function/test_force_fn.py:38-45) in one launch:
+ *   h_1 = relu(W_1 obs_a + b_1),  h_l = relu(W_l h_{l-1} + b_l),
+ *   logits = Wa h_L + ba                         (fp32, f32 matrix instructions)
+ * followed by exactly the sampling of swarm_sample_actions (same counters,
+ * same bits for the same logits).  obs [n][d_in].  widths, w and b are HOST
+ * arrays of n_hidden entries, read at call time (the launch is capturable):
+ * widths[l] the units of hidden layer l, w[l] / b[l] the device pointers of
+ * its torch Linear weight [widths[l]][widths[l - 1]] (w[0]: [widths[0]][d_in])
+ * and bias, read in place; wa [k][widths[n_hidden - 1]], ba [k].
+ * 2 <= n_hidden <= 3, every width <= 128, d_in <= 32, k <= 16; outside these
+ * limits the call returns an error and launches nothing.  out_logits [n][k]
+ * is optional (NULL: not written).  The critic head is not evaluated.  An
+ * engine's deferred build does not ride along in this launch: the stages no
+ * launch carried run at the next swarm_engine_integrate. */
+int swarm_policy_deep_sample(const float *obs, int32_t n, int32_t d_in, int32_t n_hidden,
+                             const int32_t *widths, const float *const *w,
+                             const float *const *b, const float *wa, const float *ba,
+                             int32_t k, uint64_t seed, uint64_t *state, int32_t n_state,
+                             float explore_p, const float *f_table, const float *t_table,
+                             int64_t *out_idx, float *out_logp, float *out_f, float *out_t,
+                             float *out_logits, void *stream);
+
 /* Kernel timing for measurement (bench.py's roofline of the PPO update):
  * the summed duration (ms) and count of the k_ppo_grads launches this
  * thread made through swarm_ppo_epoch_grad since the previous call (HIP
@@ -528,6 +553,36 @@ int swarm_ppo_epoch_grad(const float *x, int32_t T, int32_t S, int32_t d_in,
                          const float *ba, int32_t k, const float *wc, const float *bc,
                          float gamma, float lambda, float clip_eps, float entropy_coef,
                          void *workspace, int64_t workspace_bytes, float *grad, void *stream);
+
+/* swarm_ppo_epoch_grad for the deep actor-critic MLP of
+ * swarm_policy_deep_sample: n_hidden = 2 or 3 hidden ReLU layers, then
+ * {Dense(k) logits, Dense(1) value}.  The same loss, GAE and reference
+ * semantics (proximal_policy_loss.py:62-138, :160-168;
+ * generalized_advantage_estimate.py:42-72): R = A_raw + V differentiated
+ * through V, only the normalised advantages constant, entropy eps 1e-8.
+ * widths, w and b are HOST arrays of n_hidden entries read at call time (the
+ * launches are capturable), w / b holding device pointers of the torch
+ * Linear weights [widths[l]][widths[l - 1]] (w[0]: [widths[0]][d_in]) and
+ * biases; wa [k][widths[n_hidden - 1]], ba [k], wc [1][widths[n_hidden - 1]],
+ * bc [1].  Writes grad = d loss / d params concatenated as
+ * w1 | b1 | ... | wL | bL | wa | ba | wc | bc.  2 <= n_hidden <= 3, every
+ * width <= 128, d_in <= 32, k <= 16, T*S < 2^31: outside these limits the
+ * calls return an error (workspace_bytes: -1) and launch nothing.
+ * workspace: device memory of at least swarm_ppo_deep_workspace_bytes(...)
+ * bytes.  The products run on the f32 matrix instructions; block partials
+ * are summed in fp64 in a fixed order (deterministic, no floating-point
+ * atomics).  The optimizer step stays the caller's.  Asynchronous on
+ * `stream`. */
+int64_t swarm_ppo_deep_workspace_bytes(int32_t T, int32_t S, int32_t d_in, int32_t n_hidden,
+                                       const int32_t *widths, int32_t k);
+int swarm_ppo_deep_epoch_grad(const float *x, int32_t T, int32_t S, int32_t d_in,
+                              const int64_t *actions, const float *old_logp,
+                              const float *rewards, int32_t n_hidden, const int32_t *widths,
+                              const float *const *w, const float *const *b, const float *wa,
+                              const float *ba, int32_t k, const float *wc, const float *bc,
+                              float gamma, float lambda, float clip_eps, float entropy_coef,
+                              void *workspace, int64_t workspace_bytes, float *grad,
+                              void *stream);
 
 /* The optimizer of the PPO update (torch.optim.Adam as TorchModel builds it
  * for the optax optimizer of swarmrl/networks/flax_network.py:42-79): the six tensors

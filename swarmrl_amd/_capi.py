@@ -167,6 +167,11 @@ _SIGNATURES = {
         [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32,
          ctypes.c_uint64, _P, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P],
     ),
+    "swarm_policy_deep_sample": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32,
+         ctypes.c_uint64, _P, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P],
+    ),
     "swarm_engine_defer_build": (ctypes.c_int, [_P, _P]),
     "swarm_ppo_workspace_bytes": (
         ctypes.c_int64,
@@ -176,6 +181,16 @@ _SIGNATURES = {
         ctypes.c_int,
         [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32,
          _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+         ctypes.c_float, _P, ctypes.c_int64, _P, _P],
+    ),
+    "swarm_ppo_deep_workspace_bytes": (
+        ctypes.c_int64,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32],
+    ),
+    "swarm_ppo_deep_epoch_grad": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int32, _P, _P,
+         _P, _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float,
          ctypes.c_float, _P, ctypes.c_int64, _P, _P],
     ),
     "swarm_ppo_epoch_step": (

@@ -32,6 +32,7 @@
 #include "swarm_device.cuh"
 #include "swarm_integrator.cuh"
 #include "swarm_integrator3.cuh"
+#include "swarm_deep.cuh"
 #include "swarm_policy.cuh"
 #include "swarm_ppo.cuh"
 #include "swarm_rnd.cuh"
@@ -3414,6 +3415,58 @@ int swarm_engine_policy_mlp_sample(swarm_engine_t* e, const float* obs, int32_t 
                        f_table, t_table, out_idx, out_logp, out_f, out_t, out_logits, stream, e);
 }
 
+namespace {
+// The limits of the deep kernels (swarm_deep.cuh); null: within them.
+const char* deep_limits(int32_t d_in, int32_t n_hidden, const int32_t* widths, int32_t k) {
+  if (n_hidden < swarm::kDeepMinLayers || n_hidden > swarm::kDeepMaxLayers)
+    return "2 <= n_hidden <= 3 hidden layers";
+  if (d_in < 1 || d_in > swarm::kDeepMaxIn) return "1 <= d_in <= 32";
+  if (k < 1 || k > swarm::kDeepMaxActions) return "1 <= k <= 16 actions";
+  for (int l = 0; l < n_hidden; ++l)
+    if (widths[l] < 1 || widths[l] > swarm::kDeepMaxWidth) return "1 <= hidden width <= 128";
+  return nullptr;
+}
+}  // namespace
+
+int swarm_policy_deep_sample(const float* obs, int32_t n, int32_t d_in, int32_t n_hidden,
+                             const int32_t* widths, const float* const* w, const float* const* b,
+                             const float* wa, const float* ba, int32_t k, uint64_t seed,
+                             uint64_t* state, int32_t n_state, float explore_p,
+                             const float* f_table, const float* t_table, int64_t* out_idx,
+                             float* out_logp, float* out_f, float* out_t, float* out_logits,
+                             void* stream) {
+  if (!obs || !widths || !w || !b || !wa || !ba || !state || !f_table || !t_table || !out_idx ||
+      !out_logp || !out_f || !out_t)
+    return fail(SWARM_EINVAL, "null argument");
+  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
+  swarm::DeepArgs dp{};
+  dp.n_hidden = n_hidden;
+  for (int l = 0; l < n_hidden; ++l) {
+    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
+    dp.width[l] = widths[l];
+    dp.w[l] = w[l];
+    dp.b[l] = b[l];
+  }
+  dp.wa = wa;
+  dp.ba = ba;
+  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
+    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
+  if (n <= 0) return SWARM_OK;
+  if (n_state < (n + 63) / 64) return fail(SWARM_EINVAL, "state needs ceil(n / 64) counters");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const swarm::MlpArgs m{obs,     n,       d_in,     nullptr, nullptr, 0,     nullptr,
+                         nullptr, k,       (uint32_t)seed, (uint32_t)(seed >> 32),
+                         reinterpret_cast<unsigned long long*>(state), explore_p, f_table,
+                         t_table, out_idx, out_logp, out_f,   out_t,   out_logits};
+  const unsigned blocks = (unsigned)((n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
+  if (k <= 4)
+    hipLaunchKernelGGL(swarm::k_policy_deep_sample<4>, dim3(blocks), dim3(256), 0, s, m, dp);
+  else
+    hipLaunchKernelGGL(swarm::k_policy_deep_sample<16>, dim3(blocks), dim3(256), 0, s, m, dp);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
 int swarm_engine_defer_build(swarm_engine_t* e, int32_t* deferred) {
   if (!e || !deferred) return fail(SWARM_EINVAL, "null argument");
   *deferred = 0;
@@ -3643,6 +3696,152 @@ int swarm_ppo_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
   return ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, w1, b1, hidden, wa, ba, k, wc, bc,
                    gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
                    nullptr);
+}
+
+namespace {
+struct DeepPpoWorkspace {
+  size_t values, adv, dv, spart, partial, total;
+};
+int deep_ppo_grad_size(int d, int n_hidden, const int32_t* widths, int k) {
+  int size = 0, prev = d;
+  for (int l = 0; l < n_hidden; ++l) {
+    size += widths[l] * prev + widths[l];
+    prev = widths[l];
+  }
+  return size + k * prev + k + prev + 1;
+}
+int deep_ppo_blocks(long n) {
+  return (int)std::min<long>((n + swarm::kDeepAgents - 1) / swarm::kDeepAgents,
+                             swarm::kDeepPpoBlocks);
+}
+DeepPpoWorkspace deep_ppo_workspace(long n, long S, int size) {
+  DeepPpoWorkspace w;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  w.values = 0;
+  w.adv = up(w.values + (size_t)n * 4);
+  w.dv = up(w.adv + (size_t)n * 4);
+  w.spart = up(w.dv + (size_t)n * 4);
+  w.partial = up(w.spart + (size_t)((S + 255) / 256) * 2 * sizeof(double));
+  w.total = up(w.partial + (size_t)deep_ppo_blocks(n) * size * 4);
+  return w;
+}
+}  // namespace
+
+int64_t swarm_ppo_deep_workspace_bytes(int32_t T, int32_t S, int32_t d_in, int32_t n_hidden,
+                                       const int32_t* widths, int32_t k) {
+  if (T < 1 || S < 1 || !widths || deep_limits(d_in, n_hidden, widths, k)) return -1;
+  if ((long)T * S > INT32_MAX) return -1;
+  return (int64_t)deep_ppo_workspace((long)T * S, S,
+                                     deep_ppo_grad_size(d_in, n_hidden, widths, k)).total;
+}
+
+int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
+                              const int64_t* actions, const float* old_logp,
+                              const float* rewards, int32_t n_hidden, const int32_t* widths,
+                              const float* const* w, const float* const* b, const float* wa,
+                              const float* ba, int32_t k, const float* wc, const float* bc,
+                              float gamma, float lambda, float clip_eps, float entropy_coef,
+                              void* workspace, int64_t workspace_bytes, float* grad,
+                              void* stream) {
+  if (!x || !actions || !old_logp || !rewards || !widths || !w || !b || !wa || !ba || !wc ||
+      !bc || !workspace || !grad)
+    return fail(SWARM_EINVAL, "null argument");
+  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
+  if ((long)T * S > INT32_MAX) return fail(SWARM_ECAPACITY, "T x S < 2^31 samples");
+  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
+  swarm::DeepPpoArgs p{};
+  p.net.n_hidden = n_hidden;
+  int off = 0, prev = d_in;
+  for (int l = 0; l < n_hidden; ++l) {
+    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
+    p.net.width[l] = widths[l];
+    p.net.w[l] = w[l];
+    p.net.b[l] = b[l];
+    p.off_w[l] = off;
+    off += widths[l] * prev;
+    p.off_b[l] = off;
+    off += widths[l];
+    prev = widths[l];
+  }
+  p.net.wa = wa;
+  p.net.ba = ba;
+  p.off_wa = off;
+  off += k * prev;
+  p.off_ba = off;
+  off += k;
+  p.off_wc = off;
+  off += prev;
+  p.off_bc = off;
+  p.size = off + 1;
+  const int n = T * S;
+  const DeepPpoWorkspace ws = deep_ppo_workspace(n, S, p.size);
+  if (workspace_bytes < (int64_t)ws.total)
+    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_deep_workspace_bytes");
+  char* base = static_cast<char*>(workspace);
+  float* values = reinterpret_cast<float*>(base + ws.values);
+  float* adv = reinterpret_cast<float*>(base + ws.adv);
+  float* dv = reinterpret_cast<float*>(base + ws.dv);
+  double* spart = reinterpret_cast<double*>(base + ws.spart);
+  p.x = x;
+  p.n = n;
+  p.d = d_in;
+  p.k = k;
+  p.wc = wc;
+  p.bc = bc;
+  p.actions = actions;
+  p.old_logp = old_logp;
+  p.adv = adv;
+  p.dvalue = dv;
+  p.gae_part = spart;
+  const int gae_blocks = (S + 255) / 256;
+  p.n_part = gae_blocks;
+  p.clip_eps = clip_eps;
+  p.c_ent = entropy_coef;
+  p.partial = reinterpret_cast<float*>(base + ws.partial);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned tiles = (unsigned)(((long)n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
+  const int blocks = deep_ppo_blocks(n);
+  hipLaunchKernelGGL(swarm::k_ppo_deep_values<8>, dim3(tiles), dim3(512), 0, s, x, n, d_in, p.net,
+                     wc, bc, values);
+  // k_ppo_gae as it stands, without pack workgroups (n_gae = its grid)
+  const swarm::PpoPack none{};
+  if (T <= 32)
+    hipLaunchKernelGGL((swarm::k_ppo_gae<32, 1, 4>), dim3((unsigned)gae_blocks), dim3(256), 0, s,
+                       rewards, values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, none);
+  else
+    hipLaunchKernelGGL((swarm::k_ppo_gae<0, 1, 4>), dim3((unsigned)gae_blocks), dim3(256), 0, s,
+                       rewards, values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, none);
+  const bool three = n_hidden == 3;
+  const int lds = swarm::deep_grads_lds_floats(three) * (int)sizeof(float);
+  int dev = -1;
+  HIP_TRY(hipGetDevice(&dev));
+#define SWARM_DEEP_GRADS(KK, LL)                                                                \
+  do {                                                                                          \
+    /* more than 64 KB of dynamic LDS: allowed once per device (the first call */               \
+    /* of a size is never under capture: callers size the workspace eagerly) */                 \
+    static bool allowed[64] = {};                                                               \
+    if (dev < 0 || dev >= 64 || !allowed[dev]) {                                                \
+      HIP_TRY(hipFuncSetAttribute(                                                              \
+          reinterpret_cast<const void*>(&swarm::k_ppo_deep_grads<KK, LL>),                      \
+          hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                    \
+      if (dev >= 0 && dev < 64) allowed[dev] = true;                                            \
+    }                                                                                           \
+    hipLaunchKernelGGL((swarm::k_ppo_deep_grads<KK, LL>), dim3((unsigned)blocks), dim3(512),    \
+                       (size_t)lds, s, p);                                                      \
+  } while (0)
+  if (k <= 4 && !three)
+    SWARM_DEEP_GRADS(4, false);
+  else if (k <= 4)
+    SWARM_DEEP_GRADS(4, true);
+  else if (!three)
+    SWARM_DEEP_GRADS(16, false);
+  else
+    SWARM_DEEP_GRADS(16, true);
+#undef SWARM_DEEP_GRADS
+  hipLaunchKernelGGL(swarm::k_ppo_reduce, dim3((unsigned)((p.size + 63) / 64)), dim3(1024), 0, s,
+                     p.partial, blocks, p.size, grad);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
 }
 
 int swarm_ppo_epoch_step(const float* x, int32_t T, int32_t S, int32_t d_in,

@@ -401,6 +401,45 @@ def policy_mlp_sample(obs: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2:
     return idx, logp, f, t
 
 
+def _pointer_array(tensors):
+    """Host array of the tensors' device pointers (const float *const *)."""
+    return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
+def policy_deep_sample(obs: torch.Tensor, ws, bs, wa: torch.Tensor, ba: torch.Tensor, seed: int,
+                       state: torch.Tensor, explore_p: float, f_table: torch.Tensor,
+                       t_table: torch.Tensor, want_logits: bool = False):
+    """
+    The rollout policy of a deep actor-critic MLP in one kernel
+    (swarm_policy_deep_sample): ws / bs the 2 or 3 hidden torch Linear weights
+    and biases in order, wa / ba the actor head, all read in place; then the
+    sampling of sample_actions (same counters and bits).  obs [n, d_in] fp32
+    device.  Returns (idx, log_prob, f_swim, torque_z[, logits]).
+    """
+    obs = obs.contiguous()
+    n, d_in = obs.shape
+    k = int(wa.shape[0])
+    dev = obs.device
+    idx = torch.empty(n, dtype=torch.int64, device=dev)
+    logp = torch.empty(n, dtype=torch.float32, device=dev)
+    f = torch.empty(n, dtype=torch.float32, device=dev)
+    t = torch.empty(n, dtype=torch.float32, device=dev)
+    logits = torch.empty(n, k, dtype=torch.float32, device=dev) if want_logits else None
+    widths = (ctypes.c_int32 * len(ws))(*(int(w.shape[0]) for w in ws))
+    wp, bp = _pointer_array(ws), _pointer_array(bs)  # host arrays, read during the call
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().swarm_policy_deep_sample(
+        obs.data_ptr(), n, d_in, len(ws), ctypes.cast(widths, ctypes.c_void_p),
+        ctypes.cast(wp, ctypes.c_void_p), ctypes.cast(bp, ctypes.c_void_p),
+        wa.data_ptr(), ba.data_ptr(), k, ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+        state.data_ptr(), int(state.numel()), ctypes.c_float(explore_p), f_table.data_ptr(),
+        t_table.data_ptr(), idx.data_ptr(), logp.data_ptr(), f.data_ptr(), t.data_ptr(),
+        logits.data_ptr() if want_logits else None, ctypes.c_void_p(stream)))
+    if want_logits:
+        return idx, logp, f, t, logits
+    return idx, logp, f, t
+
+
 def adam_args(optimizer, layers):
     """swarm_adam_t for a torch Adam whose only parameters are the six PPO
     layers, or None when the fused step does not apply (another optimizer,
@@ -442,7 +481,9 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     fp32, actions [T, S] int64, old_logp / rewards [T, S] fp32 (all device),
     layers = (w1, b1, wa, ba, wc, bc) of the actor-critic MLP in torch
     layouts.  Returns the flat gradient w1 | b1 | wa | ba | wc | bc (fp32),
-    written into `out` when given.  Inputs already fp32/int64 and contiguous
+    written into `out` when given.  More than six layers: the deep MLP
+    (w1, b1, ..., wL, bL, wa, ba, wc, bc) through swarm_ppo_deep_epoch_grad,
+    the gradient in that order (no fused optimizer step: adam must be None).  Inputs already fp32/int64 and contiguous
     are used in place (no copies: the launches can be graph-captured).
     adam: a swarm_adam_t (adam_args) -- the optimizer's step then runs in the
     epoch's last launch (swarm_ppo_epoch_step) and updates the layers.
@@ -455,6 +496,11 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     T, S = int(actions.shape[0]), int(actions.shape[1])
     x = features.reshape(T * S, -1).to(torch.float32).contiguous()
     d_in = int(x.shape[1])
+    if len(layers) > 6:
+        if adam is not None:
+            raise ValueError("the fused Adam step covers the six-layer network only")
+        return _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lambda_,
+                                    clip_eps, entropy_coef, out, workspaces)
     w1, b1, wa, ba, wc, bc = layers
     hidden, k = int(w1.shape[0]), int(wa.shape[0])
     dev = x.device
@@ -462,7 +508,7 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     nbytes = int(lib.swarm_ppo_workspace_bytes(T, S, d_in, hidden, k))
     if nbytes < 0:
         raise ValueError("bad PPO sizes")
-    key = (dev.index or 0, nbytes)
+    key = ("ppo", dev.index or 0, nbytes)
     ws = workspaces.get(key) if workspaces is not None else None
     if ws is None:  # zeroed once: the fused Adam's ticket is left at zero after use
         ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -486,6 +532,47 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     _capi.check(lib.swarm_ppo_epoch_grad(
         x.data_ptr(), T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(),
         w1.data_ptr(), b1.data_ptr(), hidden, wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
+        bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
+        ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
+        ctypes.c_void_p(stream)))
+    return grad
+
+
+def _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lambda_, clip_eps,
+                         entropy_coef, out, workspaces):
+    """ppo_epoch_grad for the deep MLP (swarm_ppo_deep_epoch_grad): x [T * S, d]
+    fp32 contiguous; layers = (w1, b1, ..., wL, bL, wa, ba, wc, bc)."""
+    d_in = int(x.shape[1])
+    hidden = layers[:-4]
+    wa, ba, wc, bc = layers[-4:]
+    ws_, bs_ = list(hidden[0::2]), list(hidden[1::2])
+    k = int(wa.shape[0])
+    dev = x.device
+    lib = _capi.lib()
+    widths = (ctypes.c_int32 * len(ws_))(*(int(w.shape[0]) for w in ws_))
+    wp, bp = _pointer_array(ws_), _pointer_array(bs_)  # host arrays, read during the call
+    nbytes = int(lib.swarm_ppo_deep_workspace_bytes(T, S, d_in, len(ws_),
+                                                    ctypes.cast(widths, ctypes.c_void_p), k))
+    if nbytes < 0:
+        raise ValueError("sizes beyond the deep PPO kernels' limits")
+    key = ("ppo_deep", dev.index or 0, nbytes)
+    ws = workspaces.get(key) if workspaces is not None else None
+    if ws is None:
+        ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        if workspaces is not None:
+            workspaces[key] = ws
+    size = sum(int(t.numel()) for t in layers)
+    grad = out if out is not None else torch.empty(size, dtype=torch.float32, device=dev)
+    if grad.numel() != size or grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 tensor of the gradient's size")
+    acts = actions.to(torch.int64).contiguous()
+    olp = old_logp.to(torch.float32).contiguous()
+    rew = rewards.to(torch.float32).contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(lib.swarm_ppo_deep_epoch_grad(
+        x.data_ptr(), T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(), len(ws_),
+        ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wp, ctypes.c_void_p),
+        ctypes.cast(bp, ctypes.c_void_p), wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
         bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
         ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
         ctypes.c_void_p(stream)))

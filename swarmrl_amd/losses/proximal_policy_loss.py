@@ -6,8 +6,10 @@ loss = sum(-min(r A, clip(r, 1-eps, 1+eps) A)) - c_H * entropy
 advantages/returns from GAE on the episode's rewards and predicted values;
 n_epochs gradient steps per episode.  On the GPU, for the stock
 actor-critic MLP, each epoch's gradient comes from the fused kernels of
-swarm_ppo_epoch_grad (csrc/swarm_ppo.cuh) and torch's optimizer takes the
-step; otherwise torch autograd differentiates _calculate_loss.
+swarm_ppo_epoch_grad (csrc/swarm_ppo.cuh), for a deep one (2 or 3 hidden
+layers) from swarm_ppo_deep_epoch_grad (csrc/swarm_deep.cuh), and torch's
+optimizer takes the step; otherwise torch autograd differentiates
+_calculate_loss.
 """
 
 import os

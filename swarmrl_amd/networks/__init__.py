@@ -1,3 +1,4 @@
-from swarmrl_amd.networks.torch_network import ActorCriticMLP, TorchModel
+from swarmrl_amd.networks.torch_network import (ActorCriticMLP, DeepActorCriticMLP,
+                                                 TorchModel)
 
-__all__ = ["ActorCriticMLP", "TorchModel"]
+__all__ = ["ActorCriticMLP", "DeepActorCriticMLP", "TorchModel"]

@@ -50,6 +50,52 @@ class ActorCriticMLP(nn.Module):
                 self.critic.weight, self.critic.bias)
 
 
+class DeepActorCriticMLP(nn.Module):
+    """Dense(h_1) -> ReLU -> ... -> Dense(h_L) -> ReLU -> {Dense(n_actions)
+    logits, Dense(1) value} with L = len(hidden) hidden layers (the three
+    hidden layers of CI/unit_tests/force_function/test_force_fn.py:38-45;
+    two of 128 units is the common trainer network).  L = 2 or 3 with every
+    width <= 128 runs on the fused deep kernels (swarm_policy_deep_sample,
+    swarm_ppo_deep_epoch_grad); any other size through torch."""
+
+    def __init__(self, input_dim: int, n_actions: int = 4, hidden=(128, 128)):
+        super().__init__()
+        widths = [int(input_dim), *(int(h) for h in hidden)]
+        if len(widths) < 2:
+            raise ValueError("DeepActorCriticMLP needs at least one hidden layer")
+        self.layers = nn.ModuleList(nn.Linear(a, b) for a, b in zip(widths[:-1], widths[1:]))
+        self.actor = nn.Linear(widths[-1], n_actions)
+        self.critic = nn.Linear(widths[-1], 1)
+
+    def _trunk(self, x):
+        for layer in self.layers:
+            x = torch.relu(layer(x))
+        return x
+
+    def forward(self, x):
+        h = self._trunk(x)
+        return self.actor(h), self.critic(h)
+
+    def logits(self, x):
+        """Actor head only (the rollout never reads the value)."""
+        return self.actor(self._trunk(x))
+
+    def deep_layers(self):
+        """(ws, bs, wa, ba, wc, bc) in torch Linear layouts, ws / bs the
+        hidden layers' weights and biases in order (the fused deep kernels'
+        arguments)."""
+        return ([m.weight for m in self.layers], [m.bias for m in self.layers],
+                self.actor.weight, self.actor.bias, self.critic.weight, self.critic.bias)
+
+
+def deep_mlp_within_limits(d_in: int, hidden, k: int) -> bool:
+    """The sizes the fused deep kernels take (csrc/swarm_deep.cuh): 2 or 3
+    hidden layers, every width <= 128, d_in <= 32, k <= 16."""
+    hidden = [int(h) for h in hidden]
+    return (2 <= len(hidden) <= 3 and all(1 <= h <= 128 for h in hidden)
+            and 1 <= int(d_in) <= 32 and 1 <= int(k) <= 16)
+
+
 class TorchModel:
     """Network wrapper with the FlaxModel surface used by the agents."""
 
@@ -151,6 +197,11 @@ class TorchModel:
         if layers is not None:  # stock MLP: network + sampling in one kernel
             return ops.policy_mlp_sample(obs, *layers, self._fused_seed, self._fused_state, p,
                                          f_table, t_table, engine=engine)
+        deep = self._deep_layers(obs.shape[1], int(f_table.numel()))
+        if deep is not None:  # deep MLP: network + sampling in one kernel
+            ws, bs, wa, ba, _, _ = deep
+            return ops.policy_deep_sample(obs, ws, bs, wa, ba, self._fused_seed,
+                                          self._fused_state, p, f_table, t_table)
         if hasattr(self.model, "logits"):
             logits = self.model.logits(obs)
         else:
@@ -198,13 +249,50 @@ class TorchModel:
         ok = ok and d_in <= 16 and w1.shape[0] <= 256 and k <= 16
         return (w1, b1, w2, b2) if ok else None
 
+    def _deep_layers(self, d_in: int, k: int):
+        """(ws, bs, wa, ba, wc, bc) of a deep actor-critic MLP when the fused
+        deep kernels apply: fp32 contiguous device parameters within their
+        limits (2 <= hidden layers <= 3, every width <= 128, d_in <= 32,
+        k <= 16) that include every trainable parameter of the model; else
+        None.  SWARMRL_AMD_FUSED_DEEP=0 forces the torch path."""
+        get = getattr(self.model, "deep_layers", None)
+        if get is None or os.environ.get("SWARMRL_AMD_FUSED_DEEP", "1") == "0":
+            return None
+        ws, bs, wa, ba, wc, bc = get()
+        ws, bs = list(ws), list(bs)
+        flat = [*ws, *bs, wa, ba, wc, bc]
+        if len(bs) != len(ws) or not deep_mlp_within_limits(d_in, [w.shape[0] for w in ws], k):
+            return None
+        if not all(t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() for t in flat):
+            return None
+        widths = [d_in]
+        for w, b in zip(ws, bs):
+            if w.ndim != 2 or w.shape[1] != widths[-1] or tuple(b.shape) != (w.shape[0],):
+                return None
+            widths.append(int(w.shape[0]))
+        ok = tuple(wa.shape) == (k, widths[-1]) and tuple(ba.shape) == (k,)
+        ok = ok and tuple(wc.shape) == (1, widths[-1]) and bc.numel() == 1
+        ids = {id(t) for t in flat}
+        ok = ok and all(id(p) in ids for p in self.model.parameters() if p.requires_grad)
+        return (ws, bs, wa, ba, wc, bc) if ok else None
+
     def ppo_layers(self, d_in: int):
         """The actor-critic weights when the fused PPO gradient applies (fp32
         contiguous device parameters within swarm_ppo_epoch_grad's limits and
-        every trainable parameter among them), else None."""
+        every trainable parameter among them), else None.  For a deep MLP
+        within swarm_ppo_deep_epoch_grad's limits (_deep_layers): the flat
+        tuple (w1, b1, ..., wL, bL, wa, ba, wc, bc) of 2 L + 4 tensors, the
+        order of that kernel's gradient."""
         get = getattr(self.model, "ppo_layers", None)
-        if get is None or self.optimizer is None:
+        if self.optimizer is None:
             return None
+        if get is None:
+            deep = getattr(self.model, "deep_layers", None)
+            deep = self._deep_layers(d_in, int(deep()[2].shape[0])) if deep is not None else None
+            if deep is None:
+                return None
+            ws, bs, wa, ba, wc, bc = deep
+            return (*(t for pair in zip(ws, bs) for t in pair), wa, ba, wc, bc)
         layers = get()
         w1, b1, wa, ba, wc, bc = layers
         ok = all(t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() for t in layers)
