@@ -645,6 +645,36 @@ int swarm_rnd_env_reward(const float *x, int32_t n_envs, int32_t per_env, int32_
                          int64_t workspace_bytes, void *stream);
 int64_t swarm_rnd_env_workspace_bytes(int32_t n_envs, int32_t per_env);
 
+/* Training the RND predictor (RNDReward.update of
+ * swarmrl/intrinsic_reward/random_network_distillation.py:102-123: ZnNL
+ * SimpleTraining.train_model with MeanPowerLoss(order) and optax.adam).
+ *
+ * swarm_rnd_targets: y[a][width] = target(x[a]) for every observation a < n
+ * of x [n][d_in] (device fp32), each output summed in the order of
+ * swarm_rnd_distance's forward.  target: host array of the six device
+ * parameter pointers, as swarm_rnd_distance.
+ *
+ * swarm_rnd_train_epoch: the ceil(n / batch_size) minibatch steps of one
+ * epoch, in order, in one workgroup that keeps the predictor and its Adam
+ * moments on chip.  Step s takes the rows perm[s B .. s B + B) of x and y
+ * (perm [n] int64, a permutation of 0 .. n - 1 as torch.randperm returns it;
+ * the last batch may be short, its mean is over its own size): predictor
+ * forward, loss mean(|pred - y|^loss_order), backward, and the Adam step of
+ * swarm_ppo_epoch_step on adam's six tensors w1 | b1 | w2 | b2 | w3 | b3
+ * (torch Linear layouts), their moments and step counts, all updated in
+ * place.  Every sum runs in a fixed order and there are no floating-point
+ * atomics: the same bits on every run.  loss_out: device [ceil(n / B)],
+ * receives each step's loss; NULL to skip.  Limits: width = 32, 1 <= d_in <=
+ * 16, 1 <= batch_size <= 64, 0 <= n < 2^31, loss_order >= 1 (order 1: the
+ * gradient is sign(d), 0 at d = 0); outside them the call returns an error
+ * and launches nothing.  One launch per 32768 steps of the epoch (a bound on
+ * the run time of a launch: below 0.4 s).  Both calls are asynchronous on `stream`. */
+int swarm_rnd_targets(const float *x, int32_t n, int32_t d_in, int32_t width,
+                      const float *const *target, float *y, void *stream);
+int swarm_rnd_train_epoch(const float *x, const float *y, const int64_t *perm, int32_t n,
+                          int32_t d_in, int32_t width, int32_t batch_size, int32_t loss_order,
+                          const swarm_adam_t *adam, float *loss_out, void *stream);
+
 /* Neighbour reductions for the classical agents (all pointers device):
  * get_colloids_in_vision of bechinger_models.py:156-171 (range + cone) and
  * lymburn_model.py:113-125 (range only, half_angle < 0), fused with the

@@ -100,7 +100,8 @@ class SwarmVisionParams(ctypes.Structure):
 
 class SwarmAdam(ctypes.Structure):
     """swarm_adam_t: torch Adam's hyper-parameters and the device tensors
-    of the six PPO layers (w1 | b1 | wa | ba | wc | bc)."""
+    of the six PPO layers (w1 | b1 | wa | ba | wc | bc), or of the RND
+    predictor's (w1 | b1 | w2 | b2 | w3 | b3, swarm_rnd_train_epoch)."""
     _fields_ = [
         ("lr", ctypes.c_float),
         ("beta1", ctypes.c_float),
@@ -212,6 +213,15 @@ _SIGNATURES = {
          ctypes.c_int64, _P],
     ),
     "swarm_rnd_env_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "swarm_rnd_targets": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P],
+    ),
+    "swarm_rnd_train_epoch": (
+        ctypes.c_int,
+        [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.POINTER(SwarmAdam), _P, _P],
+    ),
     "swarm_engine_traj_ring": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "swarm_engine_traj_record": (ctypes.c_int, [_P]),
     "swarm_traj_entry_to_host": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),

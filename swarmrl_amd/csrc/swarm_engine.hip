@@ -2827,6 +2827,87 @@ int64_t swarm_rnd_env_workspace_bytes(int32_t n_envs, int32_t per_env) {
   return (int64_t)(rnd_partials_bytes(n_envs, per_env) + (size_t)n_envs * sizeof(uint32_t));
 }
 
+int swarm_rnd_targets(const float* x, int32_t n, int32_t d_in, int32_t width,
+                      const float* const* target, float* y, void* stream) {
+  if (!x || !target || !y) return fail(SWARM_EINVAL, "null argument");
+  if (width != swarm::kRndWidth) return fail(SWARM_ECAPACITY, "RND width must be 32");
+  if (d_in < 1 || d_in > swarm::kRndMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 16");
+  if (n < 0) return fail(SWARM_EINVAL, "n >= 0");
+  swarm::RndPtrs tp;
+  for (int k = 0; k < 6; ++k) {
+    if (!target[k]) return fail(SWARM_EINVAL, "null parameter");
+    tp.w[k] = target[k];
+  }
+  if (n == 0) return SWARM_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned blocks = (unsigned)(((int64_t)n + 255) / 256);
+  if (d_in <= 4)
+    hipLaunchKernelGGL(swarm::k_rnd_targets<4>, dim3(blocks), dim3(256), 0, s, x, n, d_in, tp, y);
+  else
+    hipLaunchKernelGGL(swarm::k_rnd_targets<16>, dim3(blocks), dim3(256), 0, s, x, n, d_in, tp, y);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+namespace {
+// Minibatch steps per launch of k_rnd_train: a step measured 2.6 us at B = 8
+// and 11.7 us at B = 64, so a launch stays below 0.4 s;
+// longer epochs (n / B beyond this) run as several launches on the stream,
+// the state going through torch's tensors in between.
+constexpr int kRndStepsPerLaunch = 32768;
+}  // namespace
+
+int swarm_rnd_train_epoch(const float* x, const float* y, const int64_t* perm, int32_t n,
+                          int32_t d_in, int32_t width, int32_t batch_size, int32_t loss_order,
+                          const swarm_adam_t* adam, float* loss_out, void* stream) {
+  if (!x || !y || !perm || !adam) return fail(SWARM_EINVAL, "null argument");
+  if (width != swarm::kRndWidth) return fail(SWARM_ECAPACITY, "RND width must be 32");
+  if (d_in < 1 || d_in > swarm::kRndMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 16");
+  if (batch_size < 1 || batch_size > swarm::kRndMaxBatch)
+    return fail(SWARM_ECAPACITY, "1 <= batch_size <= 64");
+  if (loss_order < 1) return fail(SWARM_EINVAL, "loss order must be an integer >= 1");
+  if (n < 0) return fail(SWARM_EINVAL, "n >= 0");
+  if (!(adam->beta1 >= 0.0f && adam->beta1 < 1.0f && adam->beta2 >= 0.0f && adam->beta2 < 1.0f))
+    return fail(SWARM_EINVAL, "Adam betas must be in [0, 1)");
+  swarm::RndTrainArgs a;
+  a.lr = adam->lr;
+  a.beta1 = adam->beta1;
+  a.beta2 = adam->beta2;
+  a.eps = adam->eps;
+  a.log2_beta1 = (float)std::log2((double)adam->beta1);
+  a.log2_beta2 = (float)std::log2((double)adam->beta2);
+  for (int t = 0; t < 6; ++t) {
+    if (!adam->param[t] || !adam->exp_avg[t] || !adam->exp_avg_sq[t] || !adam->step[t])
+      return fail(SWARM_EINVAL, "null Adam tensor");
+    a.param[t] = adam->param[t];
+    a.m[t] = adam->exp_avg[t];
+    a.v[t] = adam->exp_avg_sq[t];
+    a.step[t] = adam->step[t];
+  }
+  if (n == 0) return SWARM_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int steps = (int)(((int64_t)n + batch_size - 1) / batch_size);
+  const int R = (batch_size + 7) / 8;
+  const long long* pm = reinterpret_cast<const long long*>(perm);
+  for (int s0 = 0; s0 < steps; s0 += kRndStepsPerLaunch) {
+    const int s1 = std::min(steps, s0 + kRndStepsPerLaunch);
+    if (R == 1)
+      hipLaunchKernelGGL(swarm::k_rnd_train<1>, dim3(1), dim3(256), 0, s, x, y, pm, n, d_in,
+                         batch_size, loss_order, s0, s1, a, loss_out);
+    else if (R == 2)
+      hipLaunchKernelGGL(swarm::k_rnd_train<2>, dim3(1), dim3(256), 0, s, x, y, pm, n, d_in,
+                         batch_size, loss_order, s0, s1, a, loss_out);
+    else if (R <= 4)
+      hipLaunchKernelGGL(swarm::k_rnd_train<4>, dim3(1), dim3(256), 0, s, x, y, pm, n, d_in,
+                         batch_size, loss_order, s0, s1, a, loss_out);
+    else
+      hipLaunchKernelGGL(swarm::k_rnd_train<8>, dim3(1), dim3(256), 0, s, x, y, pm, n, d_in,
+                         batch_size, loss_order, s0, s1, a, loss_out);
+    HIP_TRY(hipGetLastError());
+  }
+  return SWARM_OK;
+}
+
 int64_t swarm_engine_step_count(const swarm_engine_t* e) {
   if (!e) return -1;
   uint64_t v = 0;

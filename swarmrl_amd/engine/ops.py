@@ -686,3 +686,78 @@ def rnd_env_reward(points: torch.Tensor, n_envs: int, target: torch.nn.Module,
         rewards.data_ptr(), ws.data_ptr(), ctypes.c_int64(ws.numel()), ctypes.c_void_p(stream)))
     return metric, env_r, rewards
 
+
+RND_MAX_BATCH = 64  # swarm_rnd_train_epoch's limit
+
+
+def _rnd_layers(net: torch.nn.Module):
+    """w1, b1, w2, b2, w3, b3 of a stock RNDArchitecture."""
+    lin = [m for m in net.modules() if isinstance(m, torch.nn.Linear)]
+    return [t for m in lin for t in (m.weight, m.bias)]
+
+
+def rnd_adam_args(optimizer, predictor: torch.nn.Module):
+    """swarm_adam_t for the torch Adam that trains the RND predictor, or None
+    when swarm_rnd_train_epoch does not apply (adam_args' screening: one
+    capturable group, no weight decay / amsgrad / maximize, float lr, the
+    state on the device in contiguous fp32)."""
+    layers = _rnd_layers(predictor)
+    if len(layers) != 6:
+        return None
+    for t in layers:
+        st = optimizer.state.get(t, {})
+        for name in ("exp_avg", "exp_avg_sq"):
+            m = st.get(name)
+            if not (isinstance(m, torch.Tensor) and m.dtype == torch.float32 and m.is_contiguous()
+                    and m.shape == t.shape and m.device == t.device):
+                return None
+        if not (isinstance(st.get("step"), torch.Tensor) and st["step"].numel() == 1
+                and st["step"].device == t.device):
+            return None
+    return adam_args(optimizer, layers)
+
+
+def rnd_targets(points: torch.Tensor, target: torch.nn.Module) -> torch.Tensor:
+    """target(points) for every observation in one launch (swarm_rnd_targets):
+    points [n, d] fp32 device, the stock RNDArchitecture; returns [n, 32]."""
+    points = points.contiguous()
+    n, d = points.shape
+    out = torch.empty(n, 32, dtype=torch.float32, device=points.device)
+    tp = _pointer_array(_rnd_layers(target))
+    stream = torch.cuda.current_stream(points.device).cuda_stream
+    _capi.check(_capi.lib().swarm_rnd_targets(
+        points.data_ptr(), n, d, 32, ctypes.cast(tp, ctypes.c_void_p), out.data_ptr(),
+        ctypes.c_void_p(stream)))
+    return out
+
+
+def rnd_train_epoch(points: torch.Tensor, targets: torch.Tensor, perm: torch.Tensor,
+                    batch_size: int, loss_order: int, adam,
+                    loss_out: torch.Tensor = None) -> None:
+    """One epoch of the RND predictor's training (swarm_rnd_train_epoch):
+    points [n, d] and targets [n, 32] fp32, perm [n] int64 (torch.randperm),
+    all contiguous on one device; adam: rnd_adam_args' swarm_adam_t -- the
+    predictor, its moments and step counts are updated in place.  loss_out:
+    optional fp32 [ceil(n / batch_size)], each step's loss."""
+    n, d = points.shape
+    if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()):
+        raise ValueError("points must be a contiguous fp32 device tensor")
+    if not (targets.dtype == torch.float32 and targets.is_contiguous()
+            and tuple(targets.shape) == (n, 32) and targets.device == points.device):
+        raise ValueError("targets must be contiguous fp32 [n, 32] on the points' device")
+    if not (perm.dtype == torch.int64 and perm.is_contiguous() and perm.numel() == n
+            and perm.device == points.device):
+        raise ValueError("perm must be contiguous int64 [n] on the points' device")
+    if n >= 2 ** 31:
+        raise ValueError("n must be below 2^31")
+    if loss_out is not None:
+        steps = -(-n // max(int(batch_size), 1))
+        if not (loss_out.dtype == torch.float32 and loss_out.is_contiguous()
+                and loss_out.numel() >= steps and loss_out.device == points.device):
+            raise ValueError("loss_out must be contiguous fp32 [ceil(n / batch_size)]")
+    stream = torch.cuda.current_stream(points.device).cuda_stream
+    _capi.check(_capi.lib().swarm_rnd_train_epoch(
+        points.data_ptr(), targets.data_ptr(), perm.data_ptr(), n, d, 32, int(batch_size),
+        int(loss_order), ctypes.byref(adam), loss_out.data_ptr() if loss_out is not None else None,
+        ctypes.c_void_p(stream)))
+
