@@ -611,6 +611,70 @@ int swarm_ppo_epoch_step(const float *x, int32_t T, int32_t S, int32_t d_in,
                          float entropy_coef, const swarm_adam_t *adam, void *workspace,
                          int64_t workspace_bytes, float *grad, void *stream);
 
+/* The rollout policy of an ensemble of n_members independent actor-critic
+ * MLPs in one launch.  Replaces the per-member policy calls of the
+ * reference's EnsembleTraining, which trains every member in a process and
+ * an engine of its own (training_routines/ensemble_submit.py:93-138).
+ * Member m owns agents [m * n_per, (m + 1) * n_per) of the flat batch:
+ * obs [n_members][n_per][d_in]; parameters stacked in torch Linear layouts,
+ * w1 [n_members][hidden][d_in], b1 [n_members][hidden],
+ * w2 [n_members][k][hidden], b2 [n_members][k]; seeds: n_members uint64 of
+ * DEVICE memory (member m's Philox key); state [n_members][n_state_per]
+ * uint64 call counters, n_state_per >= ceil(n_per / 64) (zero-initialise
+ * once).  Outputs [n_members * n_per]; out_logits [n_members * n_per][k] is
+ * optional (NULL: not written).  A workgroup serves one member; the agent
+ * index that keys Philox and the counter groups of 64 agents are local to
+ * the member, and the lanes per agent follow from n_per.
+ * Contract: member m's out_idx, out_logp, out_f, out_t, out_logits and
+ * advanced counters are bit-identical to swarm_policy_mlp_sample called on
+ * member m's slices alone with seeds[m] and state[m], whoever shares the
+ * launch.  d_in <= 16, hidden <= 256, k <= 16, 1 <= n_members <= 1024;
+ * outside these limits the call returns an error and launches nothing.
+ * Asynchronous on `stream`, capturable. */
+int swarm_policy_ensemble_sample(const float *obs, int32_t n_members, int32_t n_per,
+                                 int32_t d_in, const float *w1, const float *b1, int32_t hidden,
+                                 const float *w2, const float *b2, int32_t k,
+                                 const uint64_t *seeds, uint64_t *state, int32_t n_state_per,
+                                 float explore_p, const float *f_table, const float *t_table,
+                                 int64_t *out_idx, float *out_logp, float *out_f, float *out_t,
+                                 float *out_logits, void *stream);
+
+/* The gradient of one PPO epoch (swarm_ppo_epoch_grad) for each of
+ * n_members independent actor-critic MLPs, in the same four launches with
+ * the member as the outer grid dimension.  Replaces the per-member updates
+ * of the reference's EnsembleTraining
+ * (training_routines/ensemble_submit.py:93-138).  Data is member-major:
+ * x [n_members][T*S][d_in], actions / old_logp [n_members][T*S],
+ * rewards [n_members][T][S]; S = agent columns per member, sample t * S + col
+ * inside a member.  Parameters stacked: w1 [n_members][hidden][d_in],
+ * b1 [n_members][hidden], wa [n_members][k][hidden], ba [n_members][k],
+ * wc [n_members][1][hidden], bc [n_members][1].  grad is laid out for the
+ * stacked tensors,
+ *   w1 [M][hidden*d_in] | b1 [M][hidden] | wa [M][k*hidden] | ba [M][k] |
+ *   wc [M][hidden] | bc [M]                        (M = n_members)
+ * so consecutive views of it match the stacked parameters.  Every member
+ * has its own advantage normalisation and workspace slices, and every
+ * decision (kernel variants, number of gradient blocks) is taken from the
+ * member's own T*S; block partials are sized by the blocks a member
+ * launches.
+ * Contract: member m's segments of grad are bit-identical to
+ * swarm_ppo_epoch_grad on member m's data and parameters alone.
+ * Deterministic.  The limits of swarm_ppo_epoch_grad, and
+ * 1 <= n_members <= 1024; outside them the calls return an error
+ * (workspace_bytes: -1) and launch nothing.  workspace: device memory of at
+ * least swarm_ppo_ensemble_workspace_bytes(...) bytes.  The optimizer step
+ * stays the caller's (one elementwise Adam over the stacked tensors is
+ * n_members independent Adams).  Asynchronous on `stream`, capturable. */
+int64_t swarm_ppo_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
+                                           int32_t d_in, int32_t hidden, int32_t k);
+int swarm_ppo_ensemble_epoch_grad(const float *x, int32_t n_members, int32_t T, int32_t S,
+                                  int32_t d_in, const int64_t *actions, const float *old_logp,
+                                  const float *rewards, const float *w1, const float *b1,
+                                  int32_t hidden, const float *wa, const float *ba, int32_t k,
+                                  const float *wc, const float *bc, float gamma, float lambda,
+                                  float clip_eps, float entropy_coef, void *workspace,
+                                  int64_t workspace_bytes, float *grad, void *stream);
+
 /* Random Network Distillation distance (the intrinsic reward of
  * swarmrl/intrinsic_reward/random_network_distillation.py:126-143 with the
  * networks of rnd_configs.py:17-38): for every observation a < n of x

@@ -21,6 +21,7 @@ from swarmrl_amd import (  # noqa: F401
     sampling_strategies,
     tasks,
     trainers,
+    training_routines,
     units,
     utils,
     value_functions,

@@ -35,6 +35,7 @@
 #include "swarm_deep.cuh"
 #include "swarm_policy.cuh"
 #include "swarm_ppo.cuh"
+#include "swarm_ensemble.cuh"
 #include "swarm_rnd.cuh"
 
 namespace {
@@ -3938,6 +3939,272 @@ int swarm_ppo_epoch_step(const float* x, int32_t T, int32_t S, int32_t d_in,
                    gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
                    adam);
 }
+
+// ---- ensembles: M independent actor-critic MLPs per launch (swarm_ensemble.cuh)
+
+int swarm_policy_ensemble_sample(const float* obs, int32_t n_members, int32_t n_per,
+                                 int32_t d_in, const float* w1, const float* b1, int32_t hidden,
+                                 const float* w2, const float* b2, int32_t k,
+                                 const uint64_t* seeds, uint64_t* state, int32_t n_state_per,
+                                 float explore_p, const float* f_table, const float* t_table,
+                                 int64_t* out_idx, float* out_logp, float* out_f, float* out_t,
+                                 float* out_logits, void* stream) {
+  if (!obs || !w1 || !b1 || !w2 || !b2 || !seeds || !state || !f_table || !t_table || !out_idx ||
+      !out_logp || !out_f || !out_t)
+    return fail(SWARM_EINVAL, "null argument");
+  if (n_members < 1 || n_members > swarm::kEnsembleMaxMembers)
+    return fail(SWARM_ECAPACITY, "1 <= n_members <= 1024");
+  if (d_in < 1 || d_in > swarm::kMlpMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 16");
+  if (hidden < 1 || hidden > swarm::kMlpMaxHidden)
+    return fail(SWARM_ECAPACITY, "1 <= hidden <= 256");
+  if (k < 1 || k > swarm::kMlpMaxActions) return fail(SWARM_ECAPACITY, "1 <= k <= 16 actions");
+  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
+    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
+  if (n_per <= 0) return SWARM_OK;
+  if (n_state_per < (n_per + 63) / 64)
+    return fail(SWARM_EINVAL, "state needs ceil(n_per / 64) counters per member");
+  // lanes per agent from the member's own agent count, as policy_launch does
+  // from n: G fixes the order of the hidden-unit sum, so the logits' bits
+  const int G = n_per <= 16384 ? 4 : (n_per <= 65536 ? 2 : 1);
+  const bool small_in = d_in <= 4, small_k = k <= 4;
+  // whole blocks per member: no block, so no counter group, straddles two
+  const dim3 grid((unsigned)(((long)n_per * G + 255) / 256), (unsigned)n_members);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const swarm::EnsembleMlpArgs e{
+      swarm::MlpArgs{obs, n_per, d_in, w1, b1, hidden, w2, b2, k, 0u, 0u,
+                     reinterpret_cast<unsigned long long*>(state), explore_p, f_table, t_table,
+                     out_idx, out_logp, out_f, out_t, out_logits},
+      reinterpret_cast<const unsigned long long*>(seeds), n_state_per};
+#define SWARM_ENS_MLP(GG, DD, KK)                                                               \
+  hipLaunchKernelGGL((swarm::k_policy_ensemble_sample<GG, DD, KK>), grid, dim3(256),           \
+                     (size_t)(hidden * swarm::MlpRow<DD, KK>::kStride + KK) * sizeof(float), s, e)
+#define SWARM_ENS_MLP_G(GG)             \
+  do {                                  \
+    if (small_in && small_k)            \
+      SWARM_ENS_MLP(GG, 4, 4);          \
+    else if (small_in)                  \
+      SWARM_ENS_MLP(GG, 4, 16);         \
+    else if (small_k)                   \
+      SWARM_ENS_MLP(GG, 16, 4);         \
+    else                                \
+      SWARM_ENS_MLP(GG, 16, 16);        \
+  } while (0)
+  if (G == 4)
+    SWARM_ENS_MLP_G(4);
+  else if (G == 2)
+    SWARM_ENS_MLP_G(2);
+  else
+    SWARM_ENS_MLP_G(1);
+#undef SWARM_ENS_MLP_G
+#undef SWARM_ENS_MLP
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+namespace {
+// Every per-member decision of an ensemble epoch, taken from the member's own
+// n = T * S exactly as ppo_epoch takes it from n (the same kernel variants
+// and the same number of grads blocks, the resident-blocks cap of the
+// single-model kernel included): a member sums in the single call's order.
+struct PpoEnsemblePlan {
+  bool coop;
+  int blocks;        // grads blocks (= partial rows) per member
+  int table_floats;  // the member's parameter table
+};
+
+template <int NN, int DD, int KK>
+PpoEnsemblePlan ppo_ensemble_plan(long n) {
+  constexpr int TT = NN == 1 ? 4 : 1;
+  const long tiles128 = (n + 127) / 128;
+  PpoEnsemblePlan pl;
+  pl.coop = NN == 1 && tiles128 < 4L * swarm::kPpoBlocks;
+  pl.blocks = (int)std::min<long>(pl.coop ? tiles128 : (tiles128 + TT - 1) / TT,
+                                  swarm::kPpoBlocks);
+  if (!pl.coop) {
+    const void* fn = reinterpret_cast<const void*>(&swarm::k_ppo_grads<NN, TT, false, DD, KK>);
+    const int lds = swarm::ppo_grads_lds_floats<NN, TT, false, DD, KK>() * (int)sizeof(float);
+    if (lds > 65536)
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    pl.blocks = std::min(pl.blocks, ppo_resident_blocks(fn, 64 * NN * TT, lds));
+  }
+  pl.table_floats = 128 * NN * swarm::PpoTable<DD, KK>::kStride;
+  return pl;
+}
+
+template <int NN, int TT, bool CO, int DD, int KK>
+void ppo_ensemble_grads(const swarm::PpoEnsembleArgs& a, hipStream_t s) {
+  const void* fn =
+      reinterpret_cast<const void*>(&swarm::k_ppo_ensemble_grads<NN, TT, CO, DD, KK>);
+  const int lds = swarm::ppo_grads_lds_floats<NN, TT, CO, DD, KK>() * (int)sizeof(float);
+  if (lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((swarm::k_ppo_ensemble_grads<NN, TT, CO, DD, KK>),
+                     dim3((unsigned)a.blocks, (unsigned)a.members), dim3(64 * NN * TT),
+                     (size_t)lds, s, a);
+}
+
+// The four launches of ppo_epoch with the member index as grid dimension y.
+template <int NN, int DD, int KK>
+void ppo_ensemble_launch(swarm::PpoEnsembleArgs a, bool coop, hipStream_t s) {
+  constexpr int TT = NN == 1 ? 4 : 1;
+  const unsigned M = (unsigned)a.members;
+  const int n = a.n;
+  a.table_rows = 128 * NN;
+  const int pack_blocks = (a.table_floats + 255) / 256;
+  if (n < (1 << 20))
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_values_split<DD>),
+                       dim3((unsigned)(((long)n + 63) / 64), M), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_values<DD>),
+                       dim3((unsigned)(((n + 3) / 4 + 255) / 256), M), dim3(256), 0, s, a);
+  const dim3 ggrid((unsigned)(a.gae_blocks + pack_blocks), M);
+  if (a.T <= 32)
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<32, DD, KK>), ggrid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<0, DD, KK>), ggrid, dim3(256), 0, s, a);
+  if (NN == 1 && coop)
+    ppo_ensemble_grads<NN, TT, NN == 1, DD, KK>(a, s);
+  else
+    ppo_ensemble_grads<NN, TT, false, DD, KK>(a, s);
+  const int size = swarm::ppo_grad_size(a.d, a.hidden, a.k);
+  hipLaunchKernelGGL(swarm::k_ppo_ensemble_reduce, dim3((unsigned)((size + 63) / 64), M),
+                     dim3(1024), 0, s, a);
+}
+
+// The template widths ppo_epoch picks for (hidden, d_in, k).
+#define SWARM_ENS_PPO_H(NN, CALL)                \
+  do {                                           \
+    if (d_in == 1 && k <= 4)                     \
+      CALL(NN, 1, 4);                            \
+    else if (d_in <= 4 && k <= 4)                \
+      CALL(NN, 4, 4);                            \
+    else if (d_in <= 4)                          \
+      CALL(NN, 4, 16);                           \
+    else if (d_in <= 16 && k <= 4)               \
+      CALL(NN, 16, 4);                           \
+    else if (d_in <= 16)                         \
+      CALL(NN, 16, 16);                          \
+    else if (k <= 4)                             \
+      CALL(NN, 32, 4);                           \
+    else                                         \
+      CALL(NN, 32, 16);                          \
+  } while (0)
+#define SWARM_ENS_PPO(CALL)                      \
+  do {                                           \
+    if (hidden <= 128)                           \
+      SWARM_ENS_PPO_H(1, CALL);                  \
+    else                                         \
+      SWARM_ENS_PPO_H(2, CALL);                  \
+  } while (0)
+
+const char* ppo_ensemble_limits(int32_t M, int32_t T, int32_t S, int32_t d_in, int32_t hidden,
+                                int32_t k) {
+  if (M < 1 || M > swarm::kEnsembleMaxMembers) return "1 <= n_members <= 1024";
+  if ((long)T * S > INT32_MAX) return "T x S < 2^31 samples per member";
+  if (d_in < 1 || d_in > swarm::kPpoMaxIn) return "1 <= d_in <= 32";
+  if (hidden < 1 || hidden > swarm::kPpoMaxHidden) return "1 <= hidden <= 256";
+  if (k < 1 || k > swarm::kPpoMaxK) return "1 <= k <= 16 actions";
+  return nullptr;
+}
+
+PpoEnsemblePlan ppo_ensemble_plan_for(long n, int d_in, int hidden, int k) {
+  PpoEnsemblePlan pl{};
+#define SWARM_ENS_PLAN(NN, DD, KK) pl = ppo_ensemble_plan<NN, DD, KK>(n)
+  SWARM_ENS_PPO(SWARM_ENS_PLAN);
+#undef SWARM_ENS_PLAN
+  return pl;
+}
+
+// Member-major slices: values | adv | dv [M][n], GAE partials
+// [M][2 gae_blocks] (fp64), tables [M][table_floats], block partials
+// [M][blocks][size] -- sized by the blocks a member launches.
+struct PpoEnsembleWorkspace {
+  size_t values, adv, dv, spart, table, partial, total;
+};
+PpoEnsembleWorkspace ppo_ensemble_workspace(size_t M, size_t n, size_t S, int size,
+                                            const PpoEnsemblePlan& pl) {
+  PpoEnsembleWorkspace w;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  w.values = 0;
+  w.adv = up(w.values + M * n * 4);
+  w.dv = up(w.adv + M * n * 4);
+  w.spart = up(w.dv + M * n * 4);
+  w.table = up(w.spart + M * ((S + 255) / 256) * 2 * sizeof(double));
+  w.partial = up(w.table + M * (size_t)pl.table_floats * 4);
+  w.total = up(w.partial + M * (size_t)pl.blocks * (size_t)size * 4);
+  return w;
+}
+}  // namespace
+
+int64_t swarm_ppo_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
+                                           int32_t d_in, int32_t hidden, int32_t k) {
+  if (T < 1 || S < 1 || ppo_ensemble_limits(n_members, T, S, d_in, hidden, k)) return -1;
+  const long n = (long)T * S;
+  const PpoEnsemblePlan pl = ppo_ensemble_plan_for(n, d_in, hidden, k);
+  return (int64_t)ppo_ensemble_workspace((size_t)n_members, (size_t)n, (size_t)S,
+                                         swarm::ppo_grad_size(d_in, hidden, k), pl).total;
+}
+
+int swarm_ppo_ensemble_epoch_grad(const float* x, int32_t n_members, int32_t T, int32_t S,
+                                  int32_t d_in, const int64_t* actions, const float* old_logp,
+                                  const float* rewards, const float* w1, const float* b1,
+                                  int32_t hidden, const float* wa, const float* ba, int32_t k,
+                                  const float* wc, const float* bc, float gamma, float lambda,
+                                  float clip_eps, float entropy_coef, void* workspace,
+                                  int64_t workspace_bytes, float* grad, void* stream) {
+  if (!x || !actions || !old_logp || !rewards || !w1 || !b1 || !wa || !ba || !wc || !bc ||
+      !workspace || !grad)
+    return fail(SWARM_EINVAL, "null argument");
+  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
+  if (const char* why = ppo_ensemble_limits(n_members, T, S, d_in, hidden, k))
+    return fail(SWARM_ECAPACITY, why);
+  const int n = T * S;
+  const PpoEnsemblePlan pl = ppo_ensemble_plan_for(n, d_in, hidden, k);
+  const PpoEnsembleWorkspace ws = ppo_ensemble_workspace(
+      (size_t)n_members, (size_t)n, (size_t)S, swarm::ppo_grad_size(d_in, hidden, k), pl);
+  if (workspace_bytes < (int64_t)ws.total)
+    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_ensemble_workspace_bytes");
+  char* base = static_cast<char*>(workspace);
+  swarm::PpoEnsembleArgs a{};
+  a.x = x;
+  a.actions = actions;
+  a.old_logp = old_logp;
+  a.rewards = rewards;
+  a.w1 = w1;
+  a.b1 = b1;
+  a.wa = wa;
+  a.ba = ba;
+  a.wc = wc;
+  a.bc = bc;
+  a.T = T;
+  a.S = S;
+  a.n = n;
+  a.d = d_in;
+  a.hidden = hidden;
+  a.k = k;
+  a.members = n_members;
+  a.gamma = gamma;
+  a.lambda = lambda;
+  a.clip_eps = clip_eps;
+  a.c_ent = entropy_coef;
+  a.values = reinterpret_cast<float*>(base + ws.values);
+  a.adv = reinterpret_cast<float*>(base + ws.adv);
+  a.dv = reinterpret_cast<float*>(base + ws.dv);
+  a.spart = reinterpret_cast<double*>(base + ws.spart);
+  a.table = reinterpret_cast<float*>(base + ws.table);
+  a.partial = reinterpret_cast<float*>(base + ws.partial);
+  a.grad = grad;
+  a.gae_blocks = (S + 255) / 256;
+  a.table_floats = pl.table_floats;
+  a.blocks = pl.blocks;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define SWARM_ENS_LAUNCH(NN, DD, KK) ppo_ensemble_launch<NN, DD, KK>(a, pl.coop, s)
+  SWARM_ENS_PPO(SWARM_ENS_LAUNCH);
+#undef SWARM_ENS_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+#undef SWARM_ENS_PPO
+#undef SWARM_ENS_PPO_H
 
 int swarm_neighbor_reduce(const double* pos, const double* dir, const double* vel,
                           const int32_t* types, int32_t n_envs, int32_t n,

@@ -30,6 +30,10 @@
 // (for the gradient kernel from a per-unit table laid out beside the GAE).
 // All fp32 arithmetic with explicit fmaf; cross-sample sums in a fixed order
 // (run-to-run identical).
+//
+// Each kernel's body is a __device__ function (ppo_*_body) indexed by
+// blockIdx.x / gridDim.x only: the ensemble kernels (swarm_ensemble.cuh) run
+// the same bodies on a member's slices with the member in blockIdx.y.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -90,12 +94,12 @@ typedef float ppo_f2 __attribute__((ext_vector_type(2)));
 // registers, each unit's parameters wave-uniform scalar loads (amortised
 // over the four).
 template <int D>
-__global__ __launch_bounds__(256) void k_ppo_values(const float* __restrict__ x, int n, int d,
-                                                    const float* __restrict__ w1,
-                                                    const float* __restrict__ b1, int hidden,
-                                                    const float* __restrict__ wc,
-                                                    const float* __restrict__ bc,
-                                                    float* __restrict__ values) {
+__device__ __forceinline__ void ppo_values_body(const float* __restrict__ x, int n, int d,
+                                                const float* __restrict__ w1,
+                                                const float* __restrict__ b1, int hidden,
+                                                const float* __restrict__ wc,
+                                                const float* __restrict__ bc,
+                                                float* __restrict__ values) {
   const long s = 4 * ((long)blockIdx.x * blockDim.x + threadIdx.x);
   if (s >= n) return;
   ppo_f2 xs[2][D];
@@ -133,18 +137,27 @@ __global__ __launch_bounds__(256) void k_ppo_values(const float* __restrict__ x,
   }
 }
 
+template <int D>
+__global__ __launch_bounds__(256) void k_ppo_values(const float* __restrict__ x, int n, int d,
+                                                    const float* __restrict__ w1,
+                                                    const float* __restrict__ b1, int hidden,
+                                                    const float* __restrict__ wc,
+                                                    const float* __restrict__ bc,
+                                                    float* __restrict__ values) {
+  ppo_values_body<D>(x, n, d, w1, b1, hidden, wc, bc, values);
+}
+
 // V at small sample counts, where the per-thread chain over all units is
 // the latency: a workgroup of 4 waves takes 64 samples (lane = sample) and
 // wave w sums units [w H/4, (w + 1) H/4) (wave-uniform rows); the four
 // partials are added in a fixed order.
 template <int D>
-__global__ __launch_bounds__(256) void k_ppo_values_split(const float* __restrict__ x, int n,
-                                                          int d, const float* __restrict__ w1,
-                                                          const float* __restrict__ b1,
-                                                          int hidden,
-                                                          const float* __restrict__ wc,
-                                                          const float* __restrict__ bc,
-                                                          float* __restrict__ values) {
+__device__ __forceinline__ void ppo_values_split_body(const float* __restrict__ x, int n, int d,
+                                                      const float* __restrict__ w1,
+                                                      const float* __restrict__ b1, int hidden,
+                                                      const float* __restrict__ wc,
+                                                      const float* __restrict__ bc,
+                                                      float* __restrict__ values) {
   __shared__ float red[4][64];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -172,6 +185,17 @@ __global__ __launch_bounds__(256) void k_ppo_values_split(const float* __restric
                                    red[3][lane];
 }
 
+template <int D>
+__global__ __launch_bounds__(256) void k_ppo_values_split(const float* __restrict__ x, int n,
+                                                          int d, const float* __restrict__ w1,
+                                                          const float* __restrict__ b1,
+                                                          int hidden,
+                                                          const float* __restrict__ wc,
+                                                          const float* __restrict__ bc,
+                                                          float* __restrict__ values) {
+  ppo_values_split_body<D>(x, n, d, w1, b1, hidden, wc, bc, values);
+}
+
 // One thread per agent column of the T x S sample grid (sample t * S + col).
 // adv: raw advantages; dv: dL/dV = 0.5 huber'(V - R) minus the returns'
 // dependence on later values, dR_t/dV_u = gamma (1 - lambda) (gamma
@@ -188,12 +212,11 @@ struct PpoPack {
 };
 
 template <int TM, int D, int K>
-__global__ __launch_bounds__(256) void k_ppo_gae(const float* __restrict__ rewards,
-                                                 const float* __restrict__ values, int T, int S,
-                                                 float gamma, float lambda,
-                                                 float* __restrict__ adv, float* __restrict__ dv,
-                                                 double* __restrict__ part, int n_gae,
-                                                 PpoPack pk) {
+__device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
+                                             const float* __restrict__ values, int T, int S,
+                                             float gamma, float lambda, float* __restrict__ adv,
+                                             float* __restrict__ dv, double* __restrict__ part,
+                                             int n_gae, const PpoPack& pk) {
   __shared__ double red[2][4];
   if ((int)blockIdx.x >= n_gae) {
     ppo_pack_entry<D, K>(pk.w1, pk.b1, pk.d, pk.hidden, pk.wa, pk.k, pk.wc, pk.rows,
@@ -273,6 +296,16 @@ __global__ __launch_bounds__(256) void k_ppo_gae(const float* __restrict__ rewar
     part[2 * blockIdx.x] = a;
     part[2 * blockIdx.x + 1] = b;
   }
+}
+
+template <int TM, int D, int K>
+__global__ __launch_bounds__(256) void k_ppo_gae(const float* __restrict__ rewards,
+                                                 const float* __restrict__ values, int T, int S,
+                                                 float gamma, float lambda,
+                                                 float* __restrict__ adv, float* __restrict__ dv,
+                                                 double* __restrict__ part, int n_gae,
+                                                 PpoPack pk) {
+  ppo_gae_body<TM, D, K>(rewards, values, T, S, gamma, lambda, adv, dv, part, n_gae, pk);
 }
 
 // The sums of the GAE blocks' partials, in a fixed order (thread-strided
@@ -373,7 +406,7 @@ __device__ __forceinline__ ppo_f2 ppo_splat(float v) { return ppo_f2{v, v}; }
 // would fill 5 of every 16 rows of a v_mfma_f32_16x16x4_f32, whose f32 rate
 // is the packed-VALU rate on gfx950 (MI355X_MICROARCH.md, "Peak FP32").
 template <int NW, int NT, bool kCoop, int D, int K>
-__global__ __launch_bounds__(64 * NW * NT) void k_ppo_grads(
+__device__ __forceinline__ void ppo_grads_body(
     const float* __restrict__ x, int n, int d, const float* __restrict__ w1,
     const float* __restrict__ b1, int hidden, const float* __restrict__ wa,
     const float* __restrict__ ba, int k, const float* __restrict__ wc,
@@ -658,11 +691,26 @@ __global__ __launch_bounds__(64 * NW * NT) void k_ppo_grads(
   }
 }
 
+template <int NW, int NT, bool kCoop, int D, int K>
+__global__ __launch_bounds__(64 * NW * NT) void k_ppo_grads(
+    const float* __restrict__ x, int n, int d, const float* __restrict__ w1,
+    const float* __restrict__ b1, int hidden, const float* __restrict__ wa,
+    const float* __restrict__ ba, int k, const float* __restrict__ wc,
+    const float* __restrict__ bc, const int64_t* __restrict__ actions,
+    const float* __restrict__ old_logp, const float* __restrict__ adv,
+    const float* __restrict__ dvalue, const double* __restrict__ gae_part, int n_part,
+    const float* __restrict__ table, float clip_eps, float c_ent, float* __restrict__ partial) {
+  ppo_grads_body<NW, NT, kCoop, D, K>(x, n, d, w1, b1, hidden, wa, ba, k, wc, bc, actions,
+                                      old_logp, adv, dvalue, gae_part, n_part, table, clip_eps,
+                                      c_ent, partial);
+}
+
 // Sum of the block partials, fp64 in a fixed order.  Workgroup 1024 = 64
 // parameters x 16 block strides.
-__global__ __launch_bounds__(1024) void k_ppo_reduce(const float* __restrict__ partial,
-                                                     int n_blocks, int size,
-                                                     float* __restrict__ grad) {
+// store(p, g): where parameter p's gradient goes.
+template <typename Store>
+__device__ __forceinline__ void ppo_reduce_body(const float* __restrict__ partial, int n_blocks,
+                                                int size, Store store) {
   __shared__ double red[16][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
@@ -676,8 +724,14 @@ __global__ __launch_bounds__(1024) void k_ppo_reduce(const float* __restrict__ p
   if (w == 0 && p < size) {
     double t = 0.0;
     for (int i = 0; i < 16; ++i) t += red[i][lane];
-    grad[p] = (float)t;
+    store(p, (float)t);
   }
+}
+
+__global__ __launch_bounds__(1024) void k_ppo_reduce(const float* __restrict__ partial,
+                                                     int n_blocks, int size,
+                                                     float* __restrict__ grad) {
+  ppo_reduce_body(partial, n_blocks, size, [&](int p, float g) { grad[p] = g; });
 }
 
 // The optimizer step fused into the reduce (swarm_ppo_epoch_step): torch

@@ -579,6 +579,139 @@ def _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lam
     return grad
 
 
+def policy_ensemble_sample(obs: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                           w2: torch.Tensor, b2: torch.Tensor, seeds: torch.Tensor,
+                           state: torch.Tensor, explore_p: float, f_table: torch.Tensor,
+                           t_table: torch.Tensor, want_logits: bool = False, out=None):
+    """
+    The rollout policy of M independent actor-critic MLPs in one kernel
+    (swarm_policy_ensemble_sample).  obs [M * n_per, d_in] (or [M, n_per,
+    d_in]) fp32 device, member m owning rows [m * n_per, (m + 1) * n_per);
+    stacked torch Linear weights w1 [M, hidden, d_in], b1 [M, hidden],
+    w2 [M, k, hidden], b2 [M, k]; seeds [M] int64 device (the members' Philox
+    keys), state [M, n_state_per] int64 device counters with n_state_per >=
+    ceil(n_per / 64).  Member m's results and advanced counters are
+    bit-identical to policy_mlp_sample on its slice with seeds[m] and
+    state[m].  out: (idx, log_prob, f_swim, torque_z) to write into.
+    Returns (idx, log_prob, f_swim, torque_z[, logits]), each [M * n_per].
+    """
+    M, hidden, d_in = w1.shape
+    k = w2.shape[1]
+    if obs.dim() != 2 or obs.shape[1] != d_in:
+        obs = obs.reshape(-1, d_in)
+    if obs.dtype != torch.float32:
+        obs = obs.to(torch.float32)
+    obs = obs.contiguous()
+    n = obs.shape[0]
+    if n % M != 0:
+        raise ValueError(f"{n} observations do not divide among {M} ensemble members")
+    # the kernel indexes the stacked tensors by member: their shapes are its bounds
+    if (b1.shape != (M, hidden) or w2.shape != (M, k, hidden) or b2.shape != (M, k)
+            or not (w1.is_contiguous() and b1.is_contiguous() and w2.is_contiguous()
+                    and b2.is_contiguous())
+            or not (w1.dtype == b1.dtype == w2.dtype == b2.dtype == torch.float32)):
+        raise ValueError("stacked parameters must be contiguous fp32 [M, ...] tensors")
+    if state.dim() != 2 or state.shape[0] != M or not state.is_contiguous():
+        raise ValueError("state must be a contiguous [M, n_state_per] tensor")
+    if seeds.shape != (M,) or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+        raise ValueError("seeds must be a contiguous int64 tensor of M entries")
+    dev = obs.device
+    if out is not None:
+        idx, logp, f, t = out
+        if (idx.dtype != torch.int64 or not all(
+                o.numel() == n and o.is_contiguous() for o in out)
+                or not (logp.dtype == f.dtype == t.dtype == torch.float32)):
+            raise ValueError("out must be contiguous (int64, fp32, fp32, fp32) tensors of "
+                             "M * n_per entries")
+    else:
+        idx = torch.empty(n, dtype=torch.int64, device=dev)
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        f = torch.empty(n, dtype=torch.float32, device=dev)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+    logits = torch.empty(n, k, dtype=torch.float32, device=dev) if want_logits else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().swarm_policy_ensemble_sample(
+        obs.data_ptr(), M, n // M, d_in, w1.data_ptr(), b1.data_ptr(), hidden, w2.data_ptr(),
+        b2.data_ptr(), k, seeds.data_ptr(), state.data_ptr(), state.shape[1],
+        ctypes.c_float(explore_p), f_table.data_ptr(), t_table.data_ptr(), idx.data_ptr(),
+        logp.data_ptr(), f.data_ptr(), t.data_ptr(),
+        logits.data_ptr() if want_logits else None, ctypes.c_void_p(stream)))
+    if want_logits:
+        return idx, logp, f, t, logits
+    return idx, logp, f, t
+
+
+def ppo_ensemble_grad_size(M: int, d_in: int, hidden: int, k: int) -> int:
+    return M * (hidden * d_in + hidden + k * hidden + k + hidden + 1)
+
+
+def ppo_ensemble_workspace_bytes(M: int, T: int, S: int, d_in: int, hidden: int, k: int) -> int:
+    """swarm_ppo_ensemble_workspace_bytes; raises beyond the kernels' limits."""
+    nbytes = int(_capi.lib().swarm_ppo_ensemble_workspace_bytes(M, T, S, d_in, hidden, k))
+    if nbytes < 0:
+        raise ValueError("sizes beyond the ensemble PPO kernels' limits")
+    return nbytes
+
+
+def ppo_ensemble_epoch_grad(features: torch.Tensor, actions: torch.Tensor,
+                            old_logp: torch.Tensor, rewards: torch.Tensor, layers, gamma: float,
+                            lambda_: float, clip_eps: float, entropy_coef: float,
+                            out: torch.Tensor = None, workspaces: dict = None,
+                            workspace: torch.Tensor = None) -> torch.Tensor:
+    """
+    The gradient of one PPO epoch of M independent actor-critic MLPs
+    (swarm_ppo_ensemble_epoch_grad): member-major features [M, T, S, d] fp32,
+    actions [M, T, S] int64, old_logp / rewards [M, T, S] fp32 (all device),
+    layers = the stacked (w1 [M, hidden, d], b1 [M, hidden], wa [M, k, hidden],
+    ba [M, k], wc [M, 1, hidden], bc [M, 1]).  Returns the flat gradient in
+    the stacked tensors' order (w1 | b1 | wa | ba | wc | bc, each [M, ...]),
+    written into `out` when given; member m's part is bit-identical to
+    ppo_epoch_grad on its slices.  Inputs already fp32 / int64 and contiguous
+    are used in place (the launches can be graph-captured).  workspaces: the
+    caller's cache, as in ppo_epoch_grad; workspace: an explicit uint8 device
+    buffer instead (its size is checked by the library).
+    """
+    M, T, S = actions.shape
+    x = features.reshape(M, T * S, -1).to(torch.float32).contiguous()
+    d_in = x.shape[2]
+    w1, b1, wa, ba, wc, bc = layers
+    hidden, k = w1.shape[1], wa.shape[1]
+    # the kernels index the stacked tensors by member: their shapes are the bounds
+    if (w1.shape != (M, hidden, d_in) or b1.shape != (M, hidden) or wa.shape != (M, k, hidden)
+            or ba.shape != (M, k) or wc.shape != (M, 1, hidden) or bc.shape != (M, 1)
+            or not all(t.is_contiguous() and t.dtype == torch.float32 for t in layers)):
+        raise ValueError("stacked parameters must be contiguous fp32 [M, ...] tensors")
+    if old_logp.shape != actions.shape or rewards.shape != actions.shape:
+        raise ValueError("actions, old_logp and rewards must all be [M, T, S]")
+    dev = x.device
+    lib = _capi.lib()
+    if workspace is not None:
+        ws, nbytes = workspace, int(workspace.numel() * workspace.element_size())
+    else:
+        nbytes = ppo_ensemble_workspace_bytes(M, T, S, d_in, hidden, k)
+        key = ("ppo_ensemble", dev.index or 0, nbytes)
+        ws = workspaces.get(key) if workspaces is not None else None
+        if ws is None:
+            ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            if workspaces is not None:
+                workspaces[key] = ws
+    size = ppo_ensemble_grad_size(M, d_in, hidden, k)
+    grad = out if out is not None else torch.empty(size, dtype=torch.float32, device=dev)
+    if grad.numel() != size or grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 tensor of the gradient's size")
+    acts = actions.to(torch.int64).contiguous()
+    olp = old_logp.to(torch.float32).contiguous()
+    rew = rewards.to(torch.float32).contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(lib.swarm_ppo_ensemble_epoch_grad(
+        x.data_ptr(), M, T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(),
+        w1.data_ptr(), b1.data_ptr(), hidden, wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
+        bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
+        ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
+        ctypes.c_void_p(stream)))
+    return grad
+
+
 NB_COUNT, NB_PERCEPTION, NB_SUM_D, NB_SUM_D2, NB_SUM_DIR, NB_SUM_V = 0, 1, 2, 5, 6, 9
 
 

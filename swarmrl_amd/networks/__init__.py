@@ -1,4 +1,7 @@
+from swarmrl_amd.networks.ensemble_network import (EnsembleActorCriticMLP,
+                                                    EnsembleTorchModel)
 from swarmrl_amd.networks.torch_network import (ActorCriticMLP, DeepActorCriticMLP,
                                                  TorchModel)
 
-__all__ = ["ActorCriticMLP", "DeepActorCriticMLP", "TorchModel"]
+__all__ = ["ActorCriticMLP", "DeepActorCriticMLP", "TorchModel", "EnsembleActorCriticMLP",
+           "EnsembleTorchModel"]

@@ -1,0 +1,152 @@
+"""Ensemble (population) training: one launch for M members against the loop a
+user writes without it, M single-model calls on the members' slices.
+
+  python tools/ensemble_time.py [--members 1 8 64] [--runs 3] [--window 0.25]
+
+The workload is 64 envs x 1024 agents (65536 agents a slice), one feature,
+the stock 1-128-(4+1) network, episodes of T = 20 slices; member m owns
+64 / M envs.  Timed, for each M:
+
+  policy   the rollout policy of one slice: ops.policy_ensemble_sample
+           against M x ops.policy_mlp_sample
+  epoch    the gradient of one PPO epoch over the episode:
+           ops.ppo_ensemble_epoch_grad against M x ops.ppo_epoch_grad
+
+The loop's kernels are the single-model ones, so the loop is the baseline
+and the ensemble path the code under test; both give the same bits (checked
+here before timing).  Each figure is a host clock around back-to-back calls
+that end in a device synchronise, the call count calibrated so that a window
+lasts --window seconds, after a warm-up of every shape; --runs alternating
+runs (ensemble, loop, ensemble, ...) show the run-to-run spread.  The table
+in DESIGN.md is this tool's output."""
+import argparse
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, ".")
+from swarmrl_amd.engine import ops  # noqa: E402
+from swarmrl_amd.networks import ActorCriticMLP, EnsembleActorCriticMLP  # noqa: E402
+
+E, A, D, K, HIDDEN, T = 64, 1024, 1, 4, 128, 20
+HYPER = (0.99, 0.95, 0.2, 0.01)  # gamma, lambda, clip epsilon, entropy coefficient
+
+
+def timed(fn, seconds):
+    """us per call of fn over a window of about `seconds` (calibrated)."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    calls, t = 4, 0.0
+    while True:
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        if t >= seconds:
+            return 1e6 * t / calls
+        calls = max(calls * 2, int(calls * 1.2 * seconds / max(t, 1e-6)))
+
+
+def problem(M, dev):
+    g = torch.Generator().manual_seed(M)
+    torch.manual_seed(M)
+    ens = EnsembleActorCriticMLP.from_members(
+        [ActorCriticMLP(D, K, HIDDEN) for _ in range(M)]).to(dev)
+    n_per = E * A // M
+    p = {"M": M, "n_per": n_per, "ens": ens,
+         "obs": torch.randn(M, n_per, D, generator=g).to(dev),
+         "seeds": torch.randint(0, 2 ** 62, (M,), generator=g).to(dev),
+         "ftab": torch.tensor([0.0, 10.0, 0.0, 0.0], device=dev),
+         "ttab": torch.tensor([10.0, 0.0, -10.0, 0.0], device=dev),
+         "x": torch.randn(M, T, n_per, D, generator=g).to(dev),
+         "actions": torch.randint(0, K, (M, T, n_per), generator=g).to(dev),
+         "rewards": torch.randn(M, T, n_per, generator=g).to(dev),
+         "old": (-1.386 + 0.3 * torch.randn(M, T, n_per, generator=g)).to(dev)}
+    groups = (n_per + 63) // 64
+    p["state_e"] = torch.zeros(M, groups, dtype=torch.int64, device=dev)
+    p["state_l"] = [torch.zeros(groups, dtype=torch.int64, device=dev) for _ in range(M)]
+    p["seed_l"] = [int(s) for s in p["seeds"].tolist()]
+    p["members"] = [tuple(t[m] for t in ens.ppo_layers()) for m in range(M)]
+    p["ws_e"], p["ws_l"] = {}, {}
+    size = sum(t.numel() for t in ens.ppo_layers())
+    p["grad_e"] = torch.empty(size, device=dev)
+    p["grad_l"] = [torch.empty(size // M, device=dev) for _ in range(M)]
+    return p
+
+
+def policy_ensemble(p):
+    return ops.policy_ensemble_sample(p["obs"], *p["ens"].rollout_layers(), p["seeds"],
+                                      p["state_e"], 0.0, p["ftab"], p["ttab"])
+
+
+def policy_loop(p):
+    out = []
+    for m in range(p["M"]):
+        w1, b1, wa, ba, _, _ = p["members"][m]
+        out.append(ops.policy_mlp_sample(p["obs"][m], w1, b1, wa, ba, p["seed_l"][m],
+                                         p["state_l"][m], 0.0, p["ftab"], p["ttab"]))
+    return out
+
+
+def epoch_ensemble(p):
+    return ops.ppo_ensemble_epoch_grad(p["x"], p["actions"], p["old"], p["rewards"],
+                                       p["ens"].ppo_layers(), *HYPER, out=p["grad_e"],
+                                       workspaces=p["ws_e"])
+
+
+def epoch_loop(p):
+    for m in range(p["M"]):
+        ops.ppo_epoch_grad(p["x"][m], p["actions"][m], p["old"][m], p["rewards"][m],
+                           p["members"][m], *HYPER, out=p["grad_l"][m], workspaces=p["ws_l"])
+    return p["grad_l"]
+
+
+def check_same_bits(p):
+    a = policy_ensemble(p)
+    b = policy_loop(p)
+    for i in range(4):
+        assert torch.equal(a[i], torch.cat([o[i] for o in b])), "policy outputs differ"
+    g = epoch_ensemble(p)
+    gl = epoch_loop(p)
+    off = 0
+    for i, t in enumerate(p["ens"].ppo_layers()):
+        seg = g[off:off + t.numel()].view_as(t)
+        off += t.numel()
+        lo = sum(x.numel() for x in p["members"][0][:i])
+        for m in range(p["M"]):
+            want = gl[m][lo:lo + t[m].numel()].view_as(t[m])
+            assert torch.equal(seg[m], want), "gradients differ"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, nargs="+", default=[1, 8, 64])
+    ap.add_argument("--runs", type=int, default=3, help="alternating runs per figure")
+    ap.add_argument("--window", type=float, default=0.25, help="seconds per timed window")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ensemble_time needs a GPU: a CPU run gives no timing")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    print(f"ensemble_time: {E} envs x {A} agents, d_in {D}, 1-{HIDDEN}-({K}+1), T = {T}; "
+          f"us per call, {args.runs} alternating runs of {args.window} s windows", flush=True)
+    for M in args.members:
+        p = problem(M, dev)
+        check_same_bits(p)
+        for name, ens, loop in (("policy", policy_ensemble, policy_loop),
+                                ("epoch", epoch_ensemble, epoch_loop)):
+            te, tl = [], []
+            for _ in range(args.runs):
+                te.append(timed(lambda: ens(p), args.window))
+                tl.append(timed(lambda: loop(p), args.window))
+            me, ml = sorted(te)[len(te) // 2], sorted(tl)[len(tl) // 2]
+            print(f"M={M:3d} {name:6s} ensemble {me:9.1f} us {[round(v, 1) for v in te]}  "
+                  f"loop {ml:9.1f} us {[round(v, 1) for v in tl]}  loop/ensemble {ml / me:5.2f}",
+                  flush=True)
+
+
+if __name__ == "__main__":
+    main()
