@@ -255,6 +255,34 @@ int swarm_engine_prebuild_noise(swarm_engine_t *e, void *stream, int32_t n_steps
  * zeroes them after reading. */
 int swarm_engine_build_stats(swarm_engine_t *e, uint64_t *out4, int32_t reset);
 
+/* A window's check in the reward launch.  Latency-bound periodic 2-D engines
+ * whose pair search filters candidate lists (unless SWARMRL_AMD_DEFER_CHECK = 0
+ * at creation; other engines ignore the hint) can run the exact check of an
+ * integration window as extra workgroups of the reward launch that follows
+ * it (swarm_field_distance / swarm_field_transform after
+ * swarm_engine_defer_build) instead of a launch of its own.
+ *
+ * swarm_engine_hint_defer_check announces, for the next
+ * swarm_engine_integrate call only, that such a reward launch follows: the
+ * call then leaves the check of its last window pending.  A pending check is
+ * host-side state; it is enqueued as a launch of its own by
+ * swarm_engine_flush_check and at the head of every other entry that takes
+ * the engine, except swarm_engine_defer_build, swarm_engine_device_views and
+ * a swarm_engine_set_stream that keeps the stream (they touch no device
+ * state).  A caller that captures the stream into a graph must call
+ * swarm_engine_flush_check before the capture ends: a graph captured with the
+ * check pending would replay without it.
+ *
+ * swarm_engine_check_stats: windows whose check rode in a reward launch since
+ * creation (or the last reset), summed over the envs, by outcome: out4[0] the
+ * other workgroups, which always run ahead of the verdict, kept their
+ * results; they did their work again because out4[1] the env had big clusters
+ * (the check workgroup integrates them), out4[2] the candidate lists turned
+ * out unusable, out4[3] the window was re-run exactly. */
+int swarm_engine_hint_defer_check(swarm_engine_t *e);
+int swarm_engine_flush_check(swarm_engine_t *e);
+int swarm_engine_check_stats(swarm_engine_t *e, uint64_t *out4, int32_t reset);
+
 /* Diagnostics of the last integration window, per env (host arrays [E],
  * either may be NULL): fallback 0 = cluster path, 1 = flagged by the build
  * (cluster > 64 lanes or neighbour overflow), 2 = re-run on the global path;

@@ -252,6 +252,9 @@ _SIGNATURES = {
         [_P, ctypes.POINTER(SwarmVisionParams), _P, ctypes.c_int32, _P, _P, _P],
     ),
     "swarm_engine_build_stats": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
+    "swarm_engine_hint_defer_check": (ctypes.c_int, [_P]),
+    "swarm_engine_flush_check": (ctypes.c_int, [_P]),
+    "swarm_engine_check_stats": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
     "swarm_engine_vision_policy": (
         ctypes.c_int,
         [_P, ctypes.POINTER(SwarmVisionParams), _P, ctypes.c_int32, _P, _P, _P, _P, _P,

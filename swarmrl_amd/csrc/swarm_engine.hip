@@ -1022,10 +1022,21 @@ struct FieldArgs {
   float* out;
 };
 
-// Agent slot t (env-major) of k_field, or of a workgroup of k_field_vgrid_sort.
-__device__ __forceinline__ void field_body(const DevState& st, const FieldArgs& f, int t) {
+// Agent slot t (env-major) of k_field, or of a workgroup of k_field_vgrid_sort:
+// everything the slot stores, computed first (field_compute) so that a
+// workgroup that runs beside the window's check can hold its stores back
+// (field_store) until the check's verdict.
+struct FieldVal {
+  float a, b;       // mode 0: d_cur, d_prev; else a: the transformed value
+  uint32_t hq[3];   // the history update
+  int32_t himg[3];
+  bool live;
+};
+__device__ __forceinline__ FieldVal field_compute(const DevState& st, const FieldArgs& f, int t) {
+  FieldVal v{};
   const int A = f.n_agents * f.n_envs;
-  if (t >= A) return;
+  v.live = t < A;
+  if (!v.live) return v;
   const int e = t / f.n_agents, ai = t - e * f.n_agents;
   const int N = st.n;
   const size_t M = (size_t)st.m;
@@ -1051,25 +1062,47 @@ __device__ __forceinline__ void field_body(const DevState& st, const FieldArgs& 
     const float dc = swarm::sqrt_rn(cur[0] * cur[0] + cur[1] * cur[1] + cur[2] * cur[2]);
     const float dp = swarm::sqrt_rn(prev[0] * prev[0] + prev[1] * prev[1] + prev[2] * prev[2]);
     if (f.mode == 0) {
-      f.d_cur[t] = dc;
-      f.d_prev[t] = dp;
+      v.a = dc;
+      v.b = dp;
     } else {
       // affine decay f(d) = fa + fb * d; value = scale * (f(d_cur) - f(d_prev))
       // (concentration_field.py:102-104); mode 2 clips at 0
       // (gradient_sensing.py:117-118; NaN propagates as in torch.clamp)
       const float fc = f.fa + f.fb * dc;
       const float fp = f.fa + f.fb * dp;
-      float v = f.fscale * (fc - fp);
-      if (f.mode == 2) v = v < 0.0f ? 0.0f : v;
-      f.out[t] = v;
+      float w = f.fscale * (fc - fp);
+      if (f.mode == 2) w = w < 0.0f ? 0.0f : w;
+      v.a = w;
     }
   }
   if (f.update || f.init_only) {
     for (int a = 0; a < 3; ++a) {
-      f.hq[(size_t)a * A + t] = a < st.dims ? st.q[a * M + gi] : 0u;
-      f.himg[(size_t)a * A + t] = a < st.dims ? st.img[a * M + gi] : 0;
+      v.hq[a] = a < st.dims ? st.q[a * M + gi] : 0u;
+      v.himg[a] = a < st.dims ? st.img[a * M + gi] : 0;
     }
   }
+  return v;
+}
+__device__ __forceinline__ void field_store(const FieldArgs& f, int t, const FieldVal& v) {
+  if (!v.live) return;
+  const int A = f.n_agents * f.n_envs;
+  if (!f.init_only) {
+    if (f.mode == 0) {
+      f.d_cur[t] = v.a;
+      f.d_prev[t] = v.b;
+    } else {
+      f.out[t] = v.a;
+    }
+  }
+  if (f.update || f.init_only) {
+    for (int a = 0; a < 3; ++a) {
+      f.hq[(size_t)a * A + t] = v.hq[a];
+      f.himg[(size_t)a * A + t] = v.himg[a];
+    }
+  }
+}
+__device__ __forceinline__ void field_body(const DevState& st, const FieldArgs& f, int t) {
+  field_store(f, t, field_compute(st, f, t));
 }
 
 __global__ __launch_bounds__(256) void k_field(DevState st, FieldArgs f) {
@@ -1085,28 +1118,177 @@ __global__ __launch_bounds__(256) void k_field(DevState st, FieldArgs f) {
 // n_fb blocks per env after the grid workgroups (l1_pairs_role).
 // with_grid = 0 (a field observable, l1_pairs): no vision grid, the reward
 // carries the sort and the pair search only (its grid workgroups return).
-template <int CH>
+// CheckArgs (kCheck launches): the window's pending check rides here as
+// well, one workgroup per env with the lowest block indices of the launch
+// (swarm::check_body with k_check's arguments), and no other workgroup
+// waits for it before it starts ("The check in the
+// reward launch").  Every role runs at once on the state the run kernel
+// left, reading no word a workgroup of this launch writes (the tag of the
+// finished sort is the env's window number, vtag, with bit 63 set: never a
+// window counter + 1 of the other launches; the pair counters were reset by
+// the run launch), and publishing nothing that cannot be recomputed: the
+// sort holds its global writes back (the check reads the last sort's
+// output), the pair search takes the lists as usable and writes scratch
+// only, the field role keeps its results in registers.  Then each waits for
+// the env's verdict:
+//  - kVerdictOk (a relaxed store, no fence on either side): the window
+//    stands and its lists are usable; the held stores go out.
+//  - kVerdictRedo: the check is about to change the state (an exact re-run)
+//    or has (big clusters, which its workgroup integrates before the test),
+//    or the lists are unusable.  Every role workgroup releases what it wrote
+//    and arrives; the check workgroup, which waits for the last arrival
+//    before it re-runs, then resets the pair counters and releases
+//    kVerdictGo; the roles acquire and do their work again the way they
+//    would after k_check.
+struct CheckArgs {
+  int n_steps;
+  uint64_t* step_ctr;
+  uint32_t* arrive;
+  int lx, ly, cell_lx, cell_ly;
+};
+constexpr uint64_t kRideTag = 1ull << 63;
+
+// The check workgroup of env e.  n_roles: the other workgroups of the launch
+// that touch env e (each arrives once after kVerdictRedo).
+__device__ __forceinline__ void ride_check_role(const Derived* __restrict__ d, const DevState& st,
+                                                const Scratch& sc, int e, int E, int n_roles,
+                                                const CheckArgs& ck, unsigned char* smem) {
+  const bool big = sc.big_n[e] != 0;
+  int outcome = 0;  // index into cstats: 0 speculated, 1 big clusters, 2 lists unusable, 3 re-run
+  auto hook = [&](bool rerun, bool lists_ok) {
+    outcome = rerun ? 3 : big ? 1 : lists_ok ? 0 : 2;
+    if (outcome == 0) {
+      swarm::verdict_publish(sc, e, swarm::kVerdictOk, false);
+    } else {
+      swarm::verdict_publish(sc, e, swarm::kVerdictRedo, false);
+      swarm::verdict_arrivals(sc, e, n_roles);
+    }
+  };
+  swarm::check_body(d, st, sc, e, E, ck.n_steps, ck.step_ctr, ck.arrive, ck.lx, ck.ly, 0,
+                    ck.cell_lx, ck.cell_ly, smem, false, hook);
+  if (threadIdx.x == 0) atomicAdd(&sc.cstats[outcome], 1ull);
+  if (outcome != 0) {
+    if (threadIdx.x == 0) {  // what the roles that ran ahead left behind
+      sc.gnpairs[e] = 0;
+      sc.gnx[e] = 0;
+      __hip_atomic_store(&sc.varrive[e], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    swarm::verdict_publish(sc, e, swarm::kVerdictGo, true);
+  }
+}
+
+struct RideSortHold {
+  static constexpr bool kActive = true;
+  const Scratch& sc;
+  int e;
+  uint64_t vt;
+  __device__ __forceinline__ bool operator()() const {
+    return swarm::verdict_poll(sc, e, vt) == swarm::kVerdictOk;
+  }
+};
+
+template <int CH, bool kCheck = false>
 __global__ __launch_bounds__(1024) void k_field_vgrid_sort(FieldArgs f, int n_fblocks, DevState st,
                                                            VisionArgs va, Scratch sc, int lxb,
                                                            int lyb, const Derived* __restrict__ d,
                                                            int n_fb, const uint64_t* __restrict__ ctl,
-                                                           int with_grid) {
+                                                           int with_grid, CheckArgs ck) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int b = fused_block(2 * va.n_envs);
   const int E = va.n_envs, npb = n_fb * E;
+  int b = fused_block(2 * va.n_envs);
+  if (kCheck) {
+    if (b < E) {
+      // the field blocks with an agent slot of env b
+      const int nA = f.n_agents, T = (int)blockDim.x;
+      const int nfield = ((b + 1) * nA - 1) / T - (b * nA) / T + 1;
+      ride_check_role(d, st, sc, b, E, 1 + (with_grid ? 1 : 0) + n_fb + nfield, ck, smem);
+      return;
+    }
+    b -= E;
+  }
   if (b >= 2 * E && b < 2 * E + npb) {
+    if (kCheck) {
+      const int fb = b - 2 * E, e = fb / n_fb;
+      float* nb2 = reinterpret_cast<float*>(smem);
+      int32_t* uf = reinterpret_cast<int32_t*>(smem) + kMaxSpecies * kMaxSpecies;
+      const uint64_t vt = sc.vtag[e];  // (loaded beside the body's first loads)
+      swarm::role_begin(sc, swarm::kRolePairs);
+      uint64_t early = 0ull;
+      swarm::pair_filter_body(d, st, sc, lxb, lyb, fb % n_fb, e, vt | kRideTag, nb2, uf, true,
+                              &early);
+      if (swarm::verdict_poll(sc, e, vt, swarm::kVerdictOk, early) == swarm::kVerdictOk) {
+        if (fb % n_fb == 0 && threadIdx.x == 0) atomicAdd(&sc.stats[0], 1ull);
+      } else {
+        swarm::verdict_redo(sc, e, vt);
+        swarm::pair_filter_body(d, st, sc, lxb, lyb, fb % n_fb, e, vt | kRideTag, nb2, uf);
+      }
+      swarm::role_end(sc, swarm::kRolePairs);
+      return;
+    }
     l1_pairs_role(d, st, sc, lxb, lyb, b - 2 * E, n_fb, ctl, smem);
     return;
   }
   if (!with_grid && b >= E && b < 2 * E) return;
   const int role = b < E ? swarm::kRoleSort : b < 2 * E ? swarm::kRoleVgrid : swarm::kRoleField;
+  const int ft0 = (b - 2 * E - npb) * (int)blockDim.x;  // field role: first agent slot
+  if (kCheck) {
+    if (b < 2 * E) {
+      const int e = b < E ? b : b - E;
+      const uint64_t vt = sc.vtag[e];
+      swarm::role_begin(sc, role);
+      bool done;
+      if (b < E) {
+        done = swarm::build_sort_body<CH, RideSortHold>(st, sc, lxb, lyb, e, smem, 0ull,
+                                                        RideSortHold{sc, e, vt});
+      } else {
+        vision_grid_body(st, va, e, smem);
+        done = swarm::verdict_poll(sc, e, vt) == swarm::kVerdictOk;
+      }
+      if (!done) {
+        swarm::verdict_redo(sc, e, vt);
+        if (b < E)
+          swarm::build_sort_body<CH>(st, sc, lxb, lyb, e, smem, n_fb > 0 ? vt | kRideTag : 0ull);
+        else
+          vision_grid_body(st, va, e, smem);
+      }
+      swarm::role_end(sc, role);
+      return;
+    }
+    // the field role: every env with an agent slot in this block
+    const int A = f.n_agents * f.n_envs;
+    const int e0 = min(ft0, A - 1) / f.n_agents;
+    const int e1 = min(ft0 + (int)blockDim.x - 1, A - 1) / f.n_agents;
+    swarm::role_begin(sc, role);
+    FieldVal v = field_compute(st, f, ft0 + (int)threadIdx.x);
+    bool redo = false;
+    for (int e = e0; e <= e1; ++e)
+      if (swarm::verdict_poll(sc, e, sc.vtag[e]) != swarm::kVerdictOk) redo = true;
+    if (redo) {
+      // every arrival first (nothing of this block is stored yet), then the
+      // waits: the block waits for nothing while it owes an arrival
+      __syncthreads();
+      if (threadIdx.x == 0)
+        for (int e = e0; e <= e1; ++e)
+          if (swarm::verdict_poll(sc, e, sc.vtag[e]) != swarm::kVerdictOk)
+            __hip_atomic_fetch_add(&sc.varrive[e], 1ull, __ATOMIC_RELEASE,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      for (int e = e0; e <= e1; ++e)
+        if (swarm::verdict_poll(sc, e, sc.vtag[e]) != swarm::kVerdictOk)
+          swarm::verdict_acquire(sc, e, sc.vtag[e], swarm::kVerdictGo);
+      v = field_compute(st, f, ft0 + (int)threadIdx.x);
+    }
+    field_store(f, ft0 + (int)threadIdx.x, v);
+    swarm::role_end(sc, role);
+    return;
+  }
   swarm::role_begin(sc, role);
   if (b < E)
     swarm::build_sort_body<CH>(st, sc, lxb, lyb, b, smem, n_fb > 0 ? ctl[swarm::kCtlWin] + 1ull : 0ull);
   else if (b < 2 * E)
     vision_grid_body(st, va, b - E, smem);
   else
-    field_body(st, f, (b - 2 * E - npb) * blockDim.x + threadIdx.x);
+    field_body(st, f, ft0 + (int)threadIdx.x);
   swarm::role_end(sc, role);
 }
 
@@ -1207,6 +1389,10 @@ __global__ void k_traj_bump(uint64_t* __restrict__ count, unsigned char* __restr
 }  // namespace
 
 // =================================================================== C ABI
+// SWARMRL_AMD_DEFER_CHECK unset: the check of an eligible engine rides in
+// the reward launch (+4 % on the headline)
+constexpr bool kDeferCheckDefault = true;
+
 struct swarm_engine {
   swarm_params_t params;
   Derived derived;
@@ -1251,6 +1437,17 @@ struct swarm_engine {
   // build (1 sort, 2 pairs, 3 cluster build; 0 none) that rides along in the
   // next observable / policy launch; flushed before a window runs
   int ride_stage = 0;
+  // SWARMRL_AMD_DEFER_CHECK on an eligible engine (l1_pairs): after
+  // swarm_engine_hint_defer_check the next integrate call leaves its last
+  // window's check pending (check_pending, check_steps: its sub-steps)
+  // instead of launching k_check; the reward launch that follows carries it
+  // (launch_field), anything else flushes it first (flush_check).  Host-side
+  // state: it must not outlive a stream capture (swarm_engine_flush_check).
+  bool defer_check = false;
+  bool defer_hint = false;
+  bool check_pending = false;
+  int check_steps = 0;
+  int n_cus = 0;
   // speculative vision grid (swarm_vision_cone_persistent): the last
   // persistent call's arguments; vgrid_ready: the reward launch built the
   // grid of the current positions for them (honoured while the deferred
@@ -1378,6 +1575,8 @@ void set_lds_attributes() {
                        reinterpret_cast<const void*>(&k_vgrid_sort<16>),
                        reinterpret_cast<const void*>(&k_field_vgrid_sort<4>),
                        reinterpret_cast<const void*>(&k_field_vgrid_sort<16>),
+                       reinterpret_cast<const void*>(&k_field_vgrid_sort<4, true>),
+                       reinterpret_cast<const void*>(&k_field_vgrid_sort<16, true>),
                        reinterpret_cast<const void*>(&k_policy_cbuild<4, 4, 4>)};
   for (const void* f : fns)
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
@@ -1643,7 +1842,18 @@ int launch_check(swarm_engine* e, int n_steps) {
 // One integration window: cluster build -> cluster run -> check/fallback.
 // use_prebuilt: the build ran already; noise_ready: the noise table holds
 // this many sub-steps from the current counter.
-int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_ready) {
+// Enqueue a pending check (swarm_engine::check_pending) as a launch of its
+// own.  Every C-ABI entry that touches the engine calls this at its head.
+int flush_check(swarm_engine* e) {
+  if (!e->check_pending) return SWARM_OK;
+  e->check_pending = false;
+  return launch_check(e, e->check_steps);
+}
+
+// may_defer: the caller announced the reward launch (defer_hint) and this is
+// the call's last window.
+int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_ready,
+                  bool may_defer = false) {
   if (!use_prebuilt) {
     const int rc = launch_build(e, e->stream);
     if (rc) return rc;
@@ -1771,10 +1981,17 @@ int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_rea
     HIP_TRY(hipEventRecord(ev1, e->stream));
     e->prof_events.emplace_back(ev0, ev1);
   }
+  if (may_defer && e->defer_check && e->wide_run && e->sc.l1_pairs) {
+    e->check_pending = true;
+    e->check_steps = n_steps;
+    return SWARM_OK;
+  }
   return launch_check(e, n_steps);
 }
 
 int run_bd(swarm_engine* e, int n_steps) {
+  const bool hint = e->defer_hint;  // one-shot
+  e->defer_hint = false;
   if (e->ride_stage > 0) {  // a deferred build no launch carried along
     const int rc = flush_ride_along(e);
     if (rc) return rc;
@@ -1785,7 +2002,7 @@ int run_bd(swarm_engine* e, int n_steps) {
   e->prebuilt_noise_steps = 0;
   while (n_steps > 0) {
     const int w = std::min(n_steps, swarm::kMaxWindow);
-    const int rc = e->cluster_path ? launch_window(e, w, pre, noise_ready)
+    const int rc = e->cluster_path ? launch_window(e, w, pre, noise_ready, hint && w == n_steps)
                                    : launch_global(e, w, 0, 0.0f, 0.0f);
     if (rc) return rc;
     pre = false;
@@ -2168,6 +2385,23 @@ int swarm_engine_create(const swarm_params_t* params, int32_t n_envs, int32_t n_
     rc = rc ? rc : dev_alloc(e, &e->sc.cand_ovf, (size_t)n_envs);
     rc = rc ? rc : dev_alloc(e, &e->sc.sort_done, (size_t)n_envs);
     rc = rc ? rc : dev_alloc(e, &e->sc.stats, 4);
+    if (e->sc.l1_pairs) {
+      // a check that rides in the reward launch: window numbers, verdicts
+      // and the outcome counters in one allocation
+      uint64_t* w = nullptr;
+      rc = rc ? rc : dev_alloc(e, &w, 3 * (size_t)n_envs + 4);
+      if (!rc) {
+        e->sc.vtag = w;
+        e->sc.verdict = w + n_envs;
+        e->sc.varrive = w + 2 * (size_t)n_envs;
+        e->sc.cstats = reinterpret_cast<unsigned long long*>(w + 3 * (size_t)n_envs);
+      }
+      const char* dc = std::getenv("SWARMRL_AMD_DEFER_CHECK");
+      e->defer_check = dc ? dc[0] == '1' : kDeferCheckDefault;
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess)
+        e->n_cus = cus;
+    }
 
   }
   set_lds_attributes();
@@ -2194,6 +2428,7 @@ int swarm_engine_create(const swarm_params_t* params, int32_t n_envs, int32_t n_
 
 void swarm_engine_destroy(swarm_engine_t* e) {
   if (!e) return;
+  (void)flush_check(e);
   (void)hipDeviceSynchronize();
   if (e->d_tstamp) (void)hipFree(e->d_tstamp);
   if (e->d_rstamp) (void)hipFree(e->d_rstamp);
@@ -2212,6 +2447,10 @@ void swarm_engine_destroy(swarm_engine_t* e) {
 
 int swarm_engine_set_stream(swarm_engine_t* e, void* stream) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  // (binding the stream the engine is on already changes nothing: a pending
+  // check stays pending for the reward launch)
+  if (e->stream != reinterpret_cast<hipStream_t>(stream))
+    if (const int frc = flush_check(e)) return frc;
   e->stream = reinterpret_cast<hipStream_t>(stream);
   return SWARM_OK;
 }
@@ -2220,6 +2459,7 @@ int swarm_engine_upload_raw(swarm_engine_t* e, const uint32_t* q, const int32_t*
                             const uint32_t* ang) {
   if (e) e->prebuilt = false, e->prebuilt_noise_steps = 0, e->ride_stage = 0;
   if (!e || !q || !img || !ang) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   HIP_TRY(hipMemcpyAsync(e->st.q, q, 3 * M * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->st.img, img, 3 * M * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
@@ -2235,6 +2475,7 @@ int swarm_engine_upload_raw(swarm_engine_t* e, const uint32_t* q, const int32_t*
 
 int swarm_engine_download_raw(swarm_engine_t* e, uint32_t* q, int32_t* img, uint32_t* ang) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   if (q) HIP_TRY(hipMemcpyAsync(q, e->st.q, 3 * M * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   if (img) HIP_TRY(hipMemcpyAsync(img, e->st.img, 3 * M * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2245,6 +2486,7 @@ int swarm_engine_download_raw(swarm_engine_t* e, uint32_t* q, int32_t* img, uint
 
 int swarm_engine_upload_state(swarm_engine_t* e, const double* pos, const double* director) {
   if (!e || !pos || !director) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   std::vector<uint32_t> q(3 * M, 0u), ang(M);
   std::vector<int32_t> img(3 * M, 0);
@@ -2268,6 +2510,7 @@ int swarm_engine_upload_state(swarm_engine_t* e, const double* pos, const double
 
 int swarm_engine_download_state(swarm_engine_t* e, double* pos, double* director, double* velocity) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   std::vector<uint32_t> q(3 * M), ang(M);
   std::vector<int32_t> img(3 * M);
@@ -2308,6 +2551,7 @@ int swarm_engine_download_state(swarm_engine_t* e, double* pos, double* director
 int swarm_engine_set_actions(swarm_engine_t* e, const float* f_swim, const float* torque_z,
                              int32_t on_device) {
   if (!e || !f_swim || !torque_z) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   if (on_device == 2) {
     // bind: later launches read the caller's buffers directly (zero copy);
@@ -2327,6 +2571,7 @@ int swarm_engine_set_actions(swarm_engine_t* e, const float* f_swim, const float
 
 int swarm_engine_set_external_force(swarm_engine_t* e, const double* f_ext) {
   if (!e || !f_ext) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   std::vector<float> f(3 * M);
   for (size_t g = 0; g < M; ++g)
@@ -2338,6 +2583,7 @@ int swarm_engine_set_external_force(swarm_engine_t* e, const double* f_ext) {
 
 int swarm_engine_set_directors(swarm_engine_t* e, const double* dir, const uint8_t* mask) {
   if (!e || !dir || !mask) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   if (e->params.n_dims == 3) {  // coll.director = new_direction (espresso.py:1238-1239)
     std::vector<float> d3(3 * M);
@@ -2370,6 +2616,7 @@ int swarm_engine_set_directors(swarm_engine_t* e, const double* dir, const uint8
 
 int swarm_engine_remove_overlap(swarm_engine_t* e, int32_t n_steps, double gamma, double max_disp) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   e->prebuilt = false;
   e->ride_stage = 0;
   e->prebuilt_noise_steps = 0;
@@ -2379,6 +2626,7 @@ int swarm_engine_remove_overlap(swarm_engine_t* e, int32_t n_steps, double gamma
 
 int swarm_engine_integrate(swarm_engine_t* e, int32_t n_steps) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (n_steps < 0) return fail(SWARM_EINVAL, "n_steps must be >= 0");
   if (n_steps == 0) return SWARM_OK;
   return run_bd(e, n_steps);
@@ -2410,6 +2658,7 @@ int read_event_pairs(std::vector<std::pair<hipEvent_t, hipEvent_t>>& ev, double*
 
 int swarm_engine_profile(swarm_engine_t* e, int32_t enable, double* run_ms, int32_t* launches) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   const int rc = read_event_pairs(e->prof_events, run_ms, launches);
   e->profile = enable != 0;
   // the launch stamps of captured run nodes (allocated here: never under capture)
@@ -2426,6 +2675,7 @@ int swarm_engine_profile(swarm_engine_t* e, int32_t enable, double* run_ms, int3
 int swarm_engine_profile_graph(swarm_engine_t* e, int32_t release, float* ms_out, float* cal_out,
                                int32_t cap, int32_t* launches) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (cap < 0 || (cap > 0 && !ms_out)) return fail(SWARM_EINVAL, "ms_out needs cap entries");
   // the replay ran on a stream the engine does not know: wait for the device
   HIP_TRY(hipDeviceSynchronize());
@@ -2496,6 +2746,7 @@ __global__ void k_stamp_reset(unsigned long long* t, int n) {
 int swarm_engine_profile_stamps(swarm_engine_t* e, int32_t reset, void* stream, float* ms_out,
                                 int32_t cap, int32_t* launches) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   const int n = e->stamp_next;
   if (launches) *launches = n;
   if (!e->d_tstamp || n == 0) return SWARM_OK;
@@ -2527,6 +2778,7 @@ int swarm_engine_profile_stamps(swarm_engine_t* e, int32_t reset, void* stream, 
 int swarm_engine_profile_roles(swarm_engine_t* e, double* us_out, int32_t cap,
                                int32_t* n_roles) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (n_roles) *n_roles = swarm::kRoles;
   const int n = e->stamp_next;
   if (cap < 0 || (cap > 0 && !us_out)) return fail(SWARM_EINVAL, "us_out needs cap entries");
@@ -2561,6 +2813,7 @@ int swarm_engine_profile_roles(swarm_engine_t* e, double* us_out, int32_t cap,
 
 int swarm_engine_time_run(swarm_engine_t* e, int32_t n_steps, int32_t reps, double* run_ms) {
   if (!e || !run_ms) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   if (n_steps < 1 || n_steps > swarm::kMaxWindow || reps < 1)
     return fail(SWARM_EINVAL, "1 <= n_steps <= 128 and reps >= 1");
   if (!e->cluster_path || e->nlist_path || e->params.n_dims != 2)
@@ -2595,6 +2848,7 @@ int swarm_engine_time_run(swarm_engine_t* e, int32_t n_steps, int32_t reps, doub
 
 int swarm_engine_debug_phases(swarm_engine_t* e, uint64_t* out32) {
   if (!e || !out32) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(out32, e->sc.phase, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
 #ifdef SWARM_PHASE_TIMING
@@ -2605,6 +2859,7 @@ int swarm_engine_debug_phases(swarm_engine_t* e, uint64_t* out32) {
 
 int swarm_engine_debug_wave_stamps(swarm_engine_t* e, uint64_t* out, int32_t n_words) {
   if (!e || !out) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t cap = 4 * (size_t)e->n_envs * (e->sc.S / 64);
   if (n_words < 0 || (size_t)n_words > cap) return fail(SWARM_EINVAL, "n_words out of range");
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2615,6 +2870,7 @@ int swarm_engine_debug_wave_stamps(swarm_engine_t* e, uint64_t* out, int32_t n_w
 
 int swarm_engine_prebuild(swarm_engine_t* e, void* stream, int32_t n_steps_hint) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (n_steps_hint < 0) return fail(SWARM_EINVAL, "n_steps_hint must be >= 0");
   if (!e->cluster_path) return SWARM_OK;  // the global path has no build step
   const int rc = launch_build(e, stream ? reinterpret_cast<hipStream_t>(stream) : e->stream);
@@ -2625,6 +2881,7 @@ int swarm_engine_prebuild(swarm_engine_t* e, void* stream, int32_t n_steps_hint)
 
 int swarm_engine_prebuild_noise(swarm_engine_t* e, void* stream, int32_t n_steps_hint) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (n_steps_hint < 0) return fail(SWARM_EINVAL, "n_steps_hint must be >= 0");
   if (!e->noise_table || n_steps_hint == 0) return SWARM_OK;
   if (e->next_table_ready) return SWARM_OK;  // filled beside the last run
@@ -2637,6 +2894,7 @@ int swarm_engine_prebuild_noise(swarm_engine_t* e, void* stream, int32_t n_steps
 
 int swarm_engine_build_stats(swarm_engine_t* e, uint64_t* out4, int32_t reset) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (!e->sc.stats) {  // (not a cluster-window engine)
     if (out4) std::memset(out4, 0, 4 * sizeof(uint64_t));
     return SWARM_OK;
@@ -2650,8 +2908,38 @@ int swarm_engine_build_stats(swarm_engine_t* e, uint64_t* out4, int32_t reset) {
   return SWARM_OK;
 }
 
+int swarm_engine_hint_defer_check(swarm_engine_t* e) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  e->defer_hint = e->defer_check;
+  return SWARM_OK;
+}
+
+int swarm_engine_flush_check(swarm_engine_t* e) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  e->defer_hint = false;
+  return flush_check(e);
+}
+
+int swarm_engine_check_stats(swarm_engine_t* e, uint64_t* out4, int32_t reset) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  if (!e->sc.cstats) {  // (no check of this engine can ride in the reward launch)
+    if (out4) std::memset(out4, 0, 4 * sizeof(uint64_t));
+    return SWARM_OK;
+  }
+  if (out4) {
+    HIP_TRY(hipMemcpyAsync(out4, e->sc.cstats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                           e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  if (reset) HIP_TRY(hipMemsetAsync(e->sc.cstats, 0, 4 * sizeof(uint64_t), e->stream));
+  return SWARM_OK;
+}
+
 int swarm_engine_window_stats(swarm_engine_t* e, int32_t* fallback, int32_t* waves) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   const size_t E = (size_t)e->n_envs;
   if (fallback)
     HIP_TRY(hipMemcpyAsync(fallback, e->sc.fallback, E * sizeof(int32_t), hipMemcpyDeviceToHost,
@@ -2672,6 +2960,7 @@ static size_t traj_entry_bytes(int n, int dims) {
 int swarm_engine_traj_ring(swarm_engine_t* e, int32_t capacity, int32_t env, void** host_ring,
                            int64_t* entry_bytes) {
   if (!e || !host_ring || !entry_bytes) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   if (capacity < 1 || env < 0 || env >= e->n_envs)
     return fail(SWARM_EINVAL, "trajectory ring: capacity >= 1 and 0 <= env < n_envs");
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2703,6 +2992,7 @@ int swarm_engine_traj_ring(swarm_engine_t* e, int32_t capacity, int32_t env, voi
 
 int swarm_engine_traj_record(swarm_engine_t* e) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (!e->traj_dev) return fail(SWARM_ESTATE, "no trajectory ring (swarm_engine_traj_ring)");
   hipLaunchKernelGGL(k_traj_write, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream,
                      e->st, e->traj_env, e->traj_dev, e->traj_cap, e->traj_entry,
@@ -2911,6 +3201,9 @@ int swarm_rnd_train_epoch(const float* x, const float* y, const int64_t* perm, i
 
 int64_t swarm_engine_step_count(const swarm_engine_t* e) {
   if (!e) return -1;
+  // (the pending check advances the counter; its flush changes no field a
+  // caller of this const entry can see)
+  if (flush_check(const_cast<swarm_engine_t*>(e))) return -1;
   uint64_t v = 0;
   if (hipMemcpyAsync(&v, e->d_step, sizeof(v), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
       hipStreamSynchronize(e->stream) != hipSuccess)
@@ -2959,6 +3252,7 @@ int vision_cone_impl(swarm_engine_t* e, const swarm_vision_params_t* vp, const i
                      int32_t n_agents, const float* radii, const int32_t* types, float* out,
                      bool persistent, const swarm::MlpArgs* pol = nullptr) {
   if (!e || !vp || !agent_idx || !radii || !types || !out) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "the vision-cone kernel is 2-D only");
   if (vp->n_cones < 1 || vp->n_cones > SWARM_MAX_CONES || vp->n_types < 1 ||
       vp->n_types > SWARM_MAX_DETECTED_TYPES || vp->n_cones * vp->n_types > 2 * SWARM_MAX_CONES)
@@ -3158,6 +3452,7 @@ int swarm_engine_vision_policy(swarm_engine_t* e, const swarm_vision_params_t* v
   if (!e || !vp || !w1 || !b1 || !w2 || !b2 || !agent_state || !f_table || !t_table || !out_idx ||
       !out_logp || !out_f || !out_t)
     return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const int nb = vp->n_cones * vp->n_types;
   if (nb < 1 || nb > 4) return fail(SWARM_ECAPACITY, "the fused policy takes <= 4 cone bins");
   if (hidden < 1 || hidden > swarm::kMlpMaxHidden)
@@ -3204,21 +3499,50 @@ int launch_field(swarm_engine* e, const FieldArgs& f) {
     const size_t slds = sort_lds_bytes(e);
     const int nfb = (total + 1023) / 1024;
     const int npf = l1_blocks_per_env(e);  // l1_pairs: the pair search rides here too
-    const dim3 grid((unsigned)(nfb + (2 + npf) * e->n_envs));
     const size_t lds = l1_launch_lds(e, std::max(glds, slds));
+    if (e->check_pending) {
+      // the window's check rides along as the first workgroups of the launch
+      // while every workgroup is resident (the other roles wait for its
+      // verdict) and the check's LDS (4 KB of it static) fits
+      const dim3 cgrid((unsigned)(nfb + (3 + npf) * e->n_envs));
+      const size_t clds = std::max(lds, check_lds_bytes(e->lxg, e->lyg, e->n, e->params.n_dims));
+      if ((int)cgrid.x <= e->n_cus && clds + 4096 <= kMaxLds) {
+        const CheckArgs ck{e->check_steps,   e->d_step,         e->d_arrive, e->lxg, e->lyg,
+                           check_cell_lx(e), check_cell_ly(e)};
+        if (e->n > 4096)
+          hipLaunchKernelGGL((k_field_vgrid_sort<16, true>), cgrid, dim3(1024), clds, e->stream, f,
+                             nfb, e->st, va, e->sc, e->lxb, e->lyb, e->d_derived, npf, e->d_step,
+                             grid_too ? 1 : 0, ck);
+        else
+          hipLaunchKernelGGL((k_field_vgrid_sort<4, true>), cgrid, dim3(1024), clds, e->stream, f,
+                             nfb, e->st, va, e->sc, e->lxb, e->lyb, e->d_derived, npf, e->d_step,
+                             grid_too ? 1 : 0, ck);
+        HIP_TRY(hipGetLastError());
+        e->check_pending = false;
+        e->ride_stage = e->sc.l1_pairs ? 3 : 2;
+        e->vgrid_ready = grid_too;
+        return SWARM_OK;
+      }
+      const int rc = flush_check(e);
+      if (rc) return rc;
+    }
+    const dim3 grid((unsigned)(nfb + (2 + npf) * e->n_envs));
+    const CheckArgs ck{};
     if (e->n > 4096)
       hipLaunchKernelGGL((k_field_vgrid_sort<16>), grid, dim3(1024), lds, e->stream, f, nfb,
                          e->st, va, e->sc, e->lxb, e->lyb, e->d_derived, npf, e->d_step,
-                         grid_too ? 1 : 0);
+                         grid_too ? 1 : 0, ck);
     else
       hipLaunchKernelGGL((k_field_vgrid_sort<4>), grid, dim3(1024), lds, e->stream, f, nfb,
                          e->st, va, e->sc, e->lxb, e->lyb, e->d_derived, npf, e->d_step,
-                         grid_too ? 1 : 0);
+                         grid_too ? 1 : 0, ck);
     HIP_TRY(hipGetLastError());
     e->ride_stage = e->sc.l1_pairs ? 3 : 2;
     e->vgrid_ready = grid_too;
     return SWARM_OK;
   }
+  // no launch to carry a pending check (the last slice of an episode)
+  if (const int frc = flush_check(e)) return frc;
   hipLaunchKernelGGL(k_field, dim3((total + 255) / 256), dim3(256), 0, e->stream, e->st, f);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
@@ -3259,6 +3583,7 @@ int swarm_pair_distances(swarm_engine_t* e, const int32_t* agent_idx, int32_t n_
                          const double box_scale[3], float* out) {
   if (!e || !agent_idx || !sensed_idx || !box_scale || !out)
     return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   if (m0 < 0 || mc < 0) return fail(SWARM_EINVAL, "negative sensed range");
   if (n_agents <= 0 || mc == 0) return SWARM_OK;
   const dim3 grid((unsigned)((n_agents + 255) / 256), (unsigned)((mc + 255) / 256),
@@ -3273,6 +3598,7 @@ int swarm_pair_distances(swarm_engine_t* e, const int32_t* agent_idx, int32_t n_
 int swarm_engine_neighbor_pairs(swarm_engine_t* e, int32_t env, double cutoff, int32_t* pairs,
                                 int32_t max_pairs, int32_t* n_pairs) {
   if (!e || !pairs || !n_pairs) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   if (env < 0 || env >= e->n_envs) return fail(SWARM_EINVAL, "env out of range");
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "neighbor_pairs is 2-D only");
   if (!(2.0 * cutoff < std::min(e->params.box[0], e->params.box[1])))
@@ -3305,6 +3631,7 @@ int swarm_engine_neighbor_pairs(swarm_engine_t* e, int32_t env, double cutoff, i
 
 int swarm_engine_set_torque_xy(swarm_engine_t* e, const float* torque_xy, int32_t on_device) {
   if (!e || !torque_xy) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpyAsync(e->st.torque_xy, torque_xy, 2 * M * sizeof(float), kind, e->stream));
@@ -3314,6 +3641,7 @@ int swarm_engine_set_torque_xy(swarm_engine_t* e, const float* torque_xy, int32_
 
 int swarm_engine_upload_directors(swarm_engine_t* e, const float* dir3) {
   if (!e || !dir3) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   HIP_TRY(hipMemcpyAsync(e->st.dir3, dir3, 3 * M * sizeof(float), hipMemcpyHostToDevice,
                          e->stream));
@@ -3326,6 +3654,7 @@ int swarm_engine_upload_directors(swarm_engine_t* e, const float* dir3) {
 
 int swarm_engine_download_directors(swarm_engine_t* e, float* dir3) {
   if (!e || !dir3) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   const size_t M = (size_t)e->st.m;
   HIP_TRY(hipMemcpyAsync(dir3, e->st.dir3, 3 * M * sizeof(float), hipMemcpyDeviceToHost,
                          e->stream));
@@ -3335,6 +3664,7 @@ int swarm_engine_download_directors(swarm_engine_t* e, float* dir3) {
 
 int swarm_engine_set_walls(swarm_engine_t* e, const swarm_wall_t* walls, int32_t n_walls) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   if (n_walls < 0 || n_walls > SWARM_MAX_WALLS) return fail(SWARM_ECAPACITY, "0 <= n_walls <= 16");
   if (n_walls > 0 && !walls) return fail(SWARM_EINVAL, "null walls");
   Derived& d = e->derived;
@@ -3370,6 +3700,7 @@ int swarm_engine_set_walls(swarm_engine_t* e, const swarm_wall_t* walls, int32_t
 
 int swarm_engine_wall_violations(swarm_engine_t* e, uint64_t* count) {
   if (!e || !count) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
   unsigned long long v = 0;
   HIP_TRY(hipMemcpyAsync(&v, e->st.wall_viol, sizeof(v), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3493,6 +3824,7 @@ int swarm_engine_policy_mlp_sample(swarm_engine_t* e, const float* obs, int32_t 
                                    float* out_logp, float* out_f, float* out_t, float* out_logits,
                                    void* stream) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
   return policy_launch(obs, n, d_in, w1, b1, hidden, w2, b2, k, seed, state, n_state, explore_p,
                        f_table, t_table, out_idx, out_logp, out_f, out_t, out_logits, stream, e);
 }

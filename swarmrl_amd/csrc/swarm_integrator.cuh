@@ -275,6 +275,18 @@ struct Scratch {
   int32_t* cand_ok;   // [E] the lists hold every pair of the next window
   int32_t* cand_ovf;  // [E] a list overflowed (set by the builder, reset by k_check)
   uint64_t* sort_done;  // [E] window counter + 1 of the last finished build sort
+  // A check that rides in the reward launch (k_field_vgrid_sort<CH, true>,
+  // swarm_engine_hint_defer_check): vtag[e] numbers the env's windows (bumped
+  // by the run launch's candidate-list workgroups, so no role of the reward
+  // launch writes it and it never repeats); the check workgroup publishes
+  // verdict[e] = vtag[e] (release, agent scope) after its state writes, and
+  // the other roles of the launch acquire it before they read anything.
+  uint64_t* vtag;       // [E]
+  uint64_t* verdict;    // [E] vtag << 2 | code (verdict_publish)
+  uint64_t* varrive;    // [E] role workgroups that ran ahead and wait to redo
+  // [4] windows whose check rode in the reward launch, by outcome
+  // (swarm_engine_check_stats): speculated, waited, lists unusable, redone
+  unsigned long long* cstats;
   // [4] window statistics summed over the envs (swarm_engine_build_stats):
   // pair searches that filtered candidate lists, that waited for the fresh
   // sort, exact re-runs, windows checked
@@ -1081,11 +1093,13 @@ __device__ __forceinline__ void block_global_run_lds(const Derived* __restrict__
 
 // Advance the device noise counter once every workgroup of the launch has
 // read it (the last arriving workgroup does it).
+// n_arrive: the workgroups that arrive (0: every workgroup of the launch).
 __device__ __forceinline__ void advance_counter(uint64_t* step_ctr, uint32_t* arrive,
-                                                uint64_t step0, int n_steps) {
+                                                uint64_t step0, int n_steps,
+                                                uint32_t n_arrive = 0u) {
   if (threadIdx.x == 0) {
     const uint32_t ticket = atomicAdd(arrive, 1u);
-    if (ticket == gridDim.x - 1) {
+    if (ticket == (n_arrive ? n_arrive : gridDim.x) - 1) {
       step_ctr[kCtlStep] = step0 + (uint64_t)n_steps;
       step_ctr[kCtlWin] += 1ull;  // window counter (noise table parity)
       *arrive = 0u;
@@ -1227,10 +1241,20 @@ __device__ __forceinline__ void publish_sort(const Scratch& sc, int e, uint64_t 
     __hip_atomic_store(&sc.sort_done[e], publish, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int CH>
-__device__ __forceinline__ void build_sort_body(const DevState& st, const Scratch& sc, int lx,
+// hold (Hold::kActive; a sort that starts beside the window's check, which
+// reads the last sort's output): called by every thread after the scan,
+// before the first write to global memory; false abandons the sort (returns
+// false: the caller sorts again).  Such a sort publishes nothing and leaves
+// the pair counters alone, and resets the fallback flag only after the hold
+// (the check reads the flag).
+struct NoSortHold {
+  static constexpr bool kActive = false;
+  __device__ __forceinline__ bool operator()() const { return true; }
+};
+template <int CH, typename Hold = NoSortHold>
+__device__ __forceinline__ bool build_sort_body(const DevState& st, const Scratch& sc, int lx,
                                                 int ly, int e, unsigned char* smem,
-                                                uint64_t publish = 0) {
+                                                uint64_t publish = 0, Hold hold = Hold()) {
   const int T = blockDim.x, tid = threadIdx.x, N = st.n;
   const size_t M = (size_t)st.m, base = (size_t)e * N;
   const int ncell = 1 << (lx + ly);
@@ -1258,7 +1282,7 @@ __device__ __forceinline__ void build_sort_body(const DevState& st, const Scratc
     cid[k] = ok ? (i | (sc.multi_species ? (int32_t)st.species[i] << 24 : 0)) : -1;
   }
   for (int c = tid; c <= ncell; c += T) cnt[c] = 0;
-  if (tid == 0) {
+  if (!Hold::kActive && tid == 0) {
     if (publish == 0) {  // (else k_check reset them: the pair search runs already)
       sc.gnpairs[e] = 0;
       sc.gnx[e] = 0;
@@ -1277,6 +1301,10 @@ __device__ __forceinline__ void build_sort_body(const DevState& st, const Scratc
   block_exclusive_scan(cnt, ncell, wave_sums);
   __syncthreads();
   SWARM_STAMP(3);
+  if (Hold::kActive) {
+    if (!hold()) return false;
+    if (tid == 0) sc.fallback[e] = 0;
+  }
   int32_t* cs = sc.bcstart + (size_t)e * (ncell + 1);
   for (int c = tid; c <= ncell; c += T) cs[c] = cnt[c];
   __syncthreads();  // cnt is read above and incremented below
@@ -1331,8 +1359,8 @@ __device__ __forceinline__ void build_sort_body(const DevState& st, const Scratc
     }
     for (int k = tid; k < sc.S; k += T) sc.perm[(size_t)e * sc.S + k] = -1;
     SWARM_STAMP(5);
-    publish_sort(sc, e, publish);
-    return;
+    if (!Hold::kActive) publish_sort(sc, e, publish);
+    return true;
   }
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
@@ -1353,7 +1381,8 @@ __device__ __forceinline__ void build_sort_body(const DevState& st, const Scratc
   // last, so the stores drain in the shadow of the scatter
   for (int k = tid; k < sc.S; k += T) sc.perm[(size_t)e * sc.S + k] = -1;
   SWARM_STAMP(5);
-  publish_sort(sc, e, publish);
+  if (!Hold::kActive) publish_sort(sc, e, publish);
+  return true;
 }
 
 // Chip-wide 2-D build sort of large envs (N > 4096 outside the ride-along
@@ -1842,9 +1871,13 @@ __device__ __forceinline__ void cand_build_body(const Derived* __restrict__ d, c
 // and so is dispatched before any waiting block) and searches its cells.
 __device__ __forceinline__ void pair_filter_body(const Derived* __restrict__ d, const DevState& st,
                                                  const Scratch& sc, int lx, int ly, int bx, int e,
-                                                 uint64_t win1, float* nb2, int32_t* uf) {
-  const bool ok = sc.cand_ok[e] != 0;  // block-uniform
-  if (bx == 0 && threadIdx.x == 0) atomicAdd(&sc.stats[ok ? 0 : 1], 1ull);
+                                                 uint64_t win1, float* nb2, int32_t* uf,
+                                                 bool spec = false,
+                                                 uint64_t* early_verdict = nullptr) {
+  // spec (beside the window's check, which decides cand_ok): the lists are
+  // taken as usable, and the caller counts the window once it knows
+  const bool ok = spec || sc.cand_ok[e] != 0;  // block-uniform
+  if (!spec && bx == 0 && threadIdx.x == 0) atomicAdd(&sc.stats[ok ? 0 : 1], 1ull);
   if (!ok) {
     if (threadIdx.x == 0)
       while (__hip_atomic_load(&sc.sort_done[e], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != win1)
@@ -1905,6 +1938,11 @@ __device__ __forceinline__ void pair_filter_body(const Derived* __restrict__ d, 
   }
   const int lane = threadIdx.x & 63;
   role_mark(sc, kMarkFilterLoaded);
+  // (spec: a first look at the env's verdict, in flight beside the output
+  // reservation's round trip; by now the check has usually decided)
+  if (early_verdict && lane == 0)
+    *early_verdict =
+        __hip_atomic_load(&sc.verdict[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const bool dense = __any(found > kKeep);
   int v = wave_incl_scan(found);
   int wbase = 0;
@@ -3854,6 +3892,16 @@ __global__ __launch_bounds__(1024) void k_cluster_run_wide(const Derived* __rest
   }
   if (b < n_noise_blocks + n_cand_blocks) {  // the next window's candidate lists
     const int cb = b - n_noise_blocks, bpe = n_cand_blocks / n_envs;
+    // this window's number for a check that rides in the reward launch
+    // (Scratch::vtag; one writer per env, launches are ordered)
+    // and the next build's pair counters, whose last reader (the cluster
+    // build) ran before this launch: a pair search that starts beside the
+    // check finds them reset
+    if (sc.vtag && cb % bpe == 0 && tid == 0) {
+      sc.vtag[cb / bpe] += 1ull;
+      sc.gnpairs[cb / bpe] = 0;
+      sc.gnx[cb / bpe] = 0;
+    }
     cand_build_body(d, st, sc, lxb, lyb, cb / bpe, (cb % bpe) * (int)blockDim.x + tid);
     stamp_end(tstamp);
     return;
@@ -4236,18 +4284,30 @@ __device__ __forceinline__ bool list_holds(const uint4* __restrict__ l, int n, u
 // cell_lx, cell_ly: the window's build grid, whose counting sort left the
 // cell-sorted snapshot in global memory (sc.bsq / bsid / bcstart: every 2-D
 // build, k_build_env included); -1: scan every colloid per mover.
-__global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, DevState st,
-                                                Scratch sc, int n_steps,
-                                                uint64_t* __restrict__ step_ctr,
-                                                uint32_t* __restrict__ arrive, int lx, int ly,
-                                                int nlist, int cell_lx, int cell_ly) {
-  extern __shared__ __align__(16) unsigned char smem[];
+// The body runs in the workgroup of env e: k_check, or the check workgroup
+// of a reward launch that carries a pending check (k_field_vgrid_sort).
+// n_envs: the check workgroups of the launch (they advance the counter).
+// on_verdict(rerun, lists_ok), called by every thread once the test is
+// decided and before the workgroup writes any state or scratch a role of the
+// same launch reads (the re-run; k_check: nothing to do); reset_pairs: reset
+// the next build's pair counters (0: the launch's pair search counts in them
+// already, the caller resets them where it must).
+struct NoVerdictHook {
+  __device__ __forceinline__ void operator()(bool, bool) const {}
+};
+template <typename Hook = NoVerdictHook>
+__device__ __forceinline__ void check_body(const Derived* __restrict__ d, const DevState& st,
+                                           const Scratch& sc, int e, int n_envs, int n_steps,
+                                           uint64_t* step_ctr, uint32_t* arrive, int lx, int ly,
+                                           int nlist, int cell_lx, int cell_ly,
+                                           unsigned char* smem, bool reset_pairs = true,
+                                           Hook on_verdict = Hook()) {
   int32_t* wave_sums = reinterpret_cast<int32_t*>(smem);  // 16
   int32_t* misc = wave_sums + 16;                          // 16
   int32_t* movers = misc + 16;                             // kMaxMovers
   int32_t* cnt = movers + kMaxMovers;                      // global-path cell counts
   __shared__ PairTables pt;
-  const int e = blockIdx.x, T = blockDim.x, tid = threadIdx.x, N = st.n;
+  const int T = blockDim.x, tid = threadIdx.x, N = st.n;
   const size_t M = (size_t)st.m, base = (size_t)e * N;
   role_begin(sc, kRoleCheck);
 #ifdef SWARM_CHECK_TIMING
@@ -4482,6 +4542,7 @@ __global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, D
 #ifdef SWARM_CHECK_TIMING
   ct2 = __builtin_amdgcn_s_memrealtime();
 #endif
+  bool lists_ok = false;
   if (sc.l1_pairs) {
     // the candidate lists the run's extra workgroups built from this
     // window's start positions hold every pair of the next window's start
@@ -4500,11 +4561,13 @@ __global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, D
     } else if (!rerun && nm > 0) {
       far = !(__int_as_float(misc[7]) <= d->cand_disp);
     }
+    lists_ok = !rerun && !far && ovf == 0;
     if (tid == 0) {
-      sc.cand_ok[e] = !rerun && !far && ovf == 0 ? 1 : 0;
+      sc.cand_ok[e] = lists_ok ? 1 : 0;
       sc.cand_ovf[e] = 0;
     }
   }
+  on_verdict(rerun, lists_ok);
   if (tid == 0) {
     if (rerun) atomicAdd(&sc.stats[2], 1ull);
     atomicAdd(&sc.stats[3], 1ull);
@@ -4535,10 +4598,12 @@ __global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, D
     sc.nmov[e] = 0;
     // the next build's pair counters (an l1_pairs pair search starts before
     // its sort, so the sort cannot reset them)
-    sc.gnpairs[e] = 0;
-    sc.gnx[e] = 0;
+    if (reset_pairs) {
+      sc.gnpairs[e] = 0;
+      sc.gnx[e] = 0;
+    }
   }
-  advance_counter(step_ctr, arrive, step0, n_steps);
+  advance_counter(step_ctr, arrive, step0, n_steps, (uint32_t)n_envs);
 #ifdef SWARM_CHECK_TIMING
   if (tid == 0) {
     uint64_t* cw = sc.phase + 32 + 8 * (size_t)e;
@@ -4547,6 +4612,89 @@ __global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, D
   }
 #endif
   role_end(sc, kRoleCheck);
+}
+
+__global__ __launch_bounds__(1024) void k_check(const Derived* __restrict__ d, DevState st,
+                                                Scratch sc, int n_steps,
+                                                uint64_t* __restrict__ step_ctr,
+                                                uint32_t* __restrict__ arrive, int lx, int ly,
+                                                int nlist, int cell_lx, int cell_ly) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  check_body(d, st, sc, blockIdx.x, gridDim.x, n_steps, step_ctr, arrive, lx, ly, nlist, cell_lx,
+             cell_ly, smem);
+}
+
+// Verdict of a check that rode in the reward launch (Scratch::verdict):
+// the env's window number (Scratch::vtag) << 2 | code.
+//   kVerdictOk    the window stands and its candidate lists are usable
+//   kVerdictRedo  the roles, which all ran ahead, finish, arrive
+//                 (Scratch::varrive) and wait
+//   kVerdictGo    the check workgroup saw every arrival, re-ran the window if
+//                 it had to and reset the pair counters: the roles acquire and
+//                 do their work again, reading cand_ok like any later launch
+constexpr int kVerdictOk = 1, kVerdictRedo = 2, kVerdictGo = 3;
+
+// The check workgroup of env e publishes; release: after everything the
+// workgroup wrote (state, cand_ok, counters).
+__device__ __forceinline__ void verdict_publish(const Scratch& sc, int e, int code, bool release) {
+  const uint64_t w = sc.vtag[e] << 2 | (uint64_t)code;
+  if (release) {
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0)
+      __hip_atomic_store(&sc.verdict[e], w, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  } else if (threadIdx.x == 0) {
+    __hip_atomic_store(&sc.verdict[e], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// A role workgroup waits for env e's verdict of this window (lane 0 of every
+// wave polls; the check workgroups have the lowest block indices of the
+// launch and every workgroup is resident, so the wait ends).  No fence: the
+// caller has read nothing the check wrote.
+// tag: the env's window number (vtag[e], which the caller loaded early).
+// early: a value of the word read earlier (lane 0 of the wave), tried first.
+__device__ __forceinline__ int verdict_poll(const Scratch& sc, int e, uint64_t tag,
+                                            int at_least = kVerdictOk, uint64_t early = 0ull) {
+  int code = 0;
+  if ((threadIdx.x & 63) == 0) {
+    for (bool first = true;; first = false) {
+      const uint64_t w =
+          first && early != 0ull
+              ? early
+              : __hip_atomic_load(&sc.verdict[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      code = (int)(w & 3ull);
+      if (w >> 2 == tag && code >= at_least && (at_least != kVerdictGo || code == kVerdictGo))
+        break;
+      __builtin_amdgcn_s_sleep(2);
+    }
+  }
+  return __shfl(code, 0);
+}
+// ... and acquires what the check workgroup released before it (kVerdictGo).
+__device__ __forceinline__ void verdict_acquire(const Scratch& sc, int e, uint64_t tag,
+                                                int at_least) {
+  (void)verdict_poll(sc, e, tag, at_least);
+  __syncthreads();
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+}
+// A role workgroup that ran ahead of a kVerdictRedo: everything it wrote is
+// released, it arrives, then waits for kVerdictGo.
+__device__ __forceinline__ void verdict_redo(const Scratch& sc, int e, uint64_t tag) {
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0)
+    __hip_atomic_fetch_add(&sc.varrive[e], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  verdict_acquire(sc, e, tag, kVerdictGo);
+}
+// The check workgroup after kVerdictRedo: every role workgroup of the env
+// (n of them) has arrived.
+__device__ __forceinline__ void verdict_arrivals(const Scratch& sc, int e, int n) {
+  if (threadIdx.x == 0)
+    while (__hip_atomic_load(&sc.varrive[e], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) !=
+           (uint64_t)n)
+      __builtin_amdgcn_s_sleep(8);
+  __syncthreads();
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
 }
 
 }  // namespace swarm

@@ -988,7 +988,11 @@ class SwarmEngine(Engine):
         self._native.call("swarm_engine_prebuild", ctypes.c_void_p(side.cuda_stream), int(n_steps))
         self._prebuild_pending = (side, None, 0)
 
-    def _run(self, n_steps: int):
+    def _run(self, n_steps: int, defer_check: bool = False):
+        """defer_check: the caller goes on to _prebuild (a ride-along build)
+        and the reward launch, which can carry the last window's check
+        (swarm_engine_hint_defer_check); the caller flushes what stays pending
+        (swarm_engine_flush_check)."""
         if self._prebuild_pending is not None and self._prebuild_pending[0] == "ride":
             # stages no launch carried along run in swarm_engine_integrate
             self._prebuild_pending = None
@@ -1007,6 +1011,8 @@ class SwarmEngine(Engine):
             torch.cuda.current_stream().wait_stream(side)
             self._prebuild_pending = None
         self._native.bind_stream()
+        if defer_check:
+            self._native.call("swarm_engine_hint_defer_check")
         self._native.call("swarm_engine_integrate", int(n_steps))
         self.system.time += n_steps * self._time_step
         self._steps_run += n_steps
@@ -1055,11 +1061,14 @@ class SwarmEngine(Engine):
             steps_to_next_slice = self.params.steps_per_slice * self.slice_idx - self.step_idx
             steps_to_next = min(steps_to_next_write, steps_to_next_slice)
 
-            self._run(steps_to_next)
             nxt = self.step_idx + steps_to_next
-            if (device_path and self.overlap_build and self.early_fork
-                    and nxt == self.params.steps_per_slice * self.slice_idx
-                    and nxt < self.params.steps_per_slice * (old_slice_idx + n_slices)):
+            early = (device_path and self.overlap_build and self.early_fork
+                     and nxt == self.params.steps_per_slice * self.slice_idx
+                     and nxt < self.params.steps_per_slice * (old_slice_idx + n_slices))
+            # the reward launch of a slice with a ride-along build can carry
+            # this chunk's last check beside the build's first stage
+            self._run(steps_to_next, defer_check=bool(early and self._ride_along))
+            if early:
                 # the next slice's cluster build depends on the positions
                 # only: fork it now, so it overlaps this chunk's reward as
                 # well as the next slice's observables and policy
@@ -1067,6 +1076,9 @@ class SwarmEngine(Engine):
             if force_model is not None:
                 force_model.calc_reward(self.swarm_view() if device_path else self.colloids)
             self.step_idx += steps_to_next
+        # a check no reward launch carried: host-side state must not outlive
+        # this call (a stream capture around it would replay without the check)
+        self._native.call("swarm_engine_flush_check")
 
     def finalize(self):
         """Write the last trajectory chunk (espresso.py:1310-1318)."""
