@@ -703,6 +703,83 @@ int swarm_ppo_ensemble_epoch_grad(const float *x, int32_t n_members, int32_t T, 
                                   float clip_eps, float entropy_coef, void *workspace,
                                   int64_t workspace_bytes, float *grad, void *stream);
 
+/* The rollout policy of an ensemble of n_members independent deep
+ * actor-critic MLPs (swarm_policy_deep_sample's network: n_hidden = 2 or 3
+ * hidden ReLU layers) in one launch.  Replaces the per-member policy calls
+ * of the reference's EnsembleTraining, one process and engine per member
+ * (training_routines/ensemble_submit.py:93-138).  Member m owns agents
+ * [m * n_per, (m + 1) * n_per): obs [n_members][n_per][d_in].  widths, w and
+ * b are HOST arrays of n_hidden entries read at call time; w[l] is the
+ * device pointer of the stacked [n_members][widths[l]][widths[l-1]]
+ * (widths[-1] = d_in), b[l] of [n_members][widths[l]];
+ * wa [n_members][k][widths[n_hidden-1]], ba [n_members][k].  seeds:
+ * n_members uint64 of DEVICE memory; state [n_members][n_state_per] uint64
+ * call counters, n_state_per >= ceil(n_per / 64) (zero-initialise once).
+ * Outputs [n_members * n_per]; out_logits [n_members * n_per][k] is optional
+ * (NULL: not written).  A workgroup is one counter group of 64 agents of
+ * one member; agent and group indices are local to the member.
+ * Contract: member m's out_idx, out_logp, out_f, out_t, out_logits and
+ * advanced counters are bit-identical to swarm_policy_deep_sample called on
+ * member m's slices alone with seeds[m] and state[m], whoever shares the
+ * launch.  The limits of swarm_policy_deep_sample (2 <= n_hidden <= 3,
+ * widths <= 128, d_in <= 32, k <= 16) and 1 <= n_members <= 1024; outside
+ * them the call returns an error and launches nothing.  Asynchronous on
+ * `stream`, capturable. */
+int swarm_policy_deep_ensemble_sample(const float *obs, int32_t n_members, int32_t n_per,
+                                      int32_t d_in, int32_t n_hidden, const int32_t *widths,
+                                      const float *const *w, const float *const *b,
+                                      const float *wa, const float *ba, int32_t k,
+                                      const uint64_t *seeds, uint64_t *state,
+                                      int32_t n_state_per, float explore_p, const float *f_table,
+                                      const float *t_table, int64_t *out_idx, float *out_logp,
+                                      float *out_f, float *out_t, float *out_logits,
+                                      void *stream);
+
+/* The gradient of one PPO epoch (swarm_ppo_deep_epoch_grad) for each of
+ * n_members independent deep actor-critic MLPs, in the same four launches
+ * with the member as the outer grid dimension.  Replaces the per-member
+ * updates of the reference's EnsembleTraining
+ * (training_routines/ensemble_submit.py:93-138).  Data is member-major as
+ * in swarm_ppo_ensemble_epoch_grad: x [n_members][T*S][d_in], actions /
+ * old_logp [n_members][T*S], rewards [n_members][T][S].  widths, w and b are
+ * HOST arrays read at call time, w[l] / b[l] the device pointers of the
+ * stacked [n_members][widths[l]][widths[l-1]] / [n_members][widths[l]];
+ * wa [n_members][k][H], ba [n_members][k], wc [n_members][1][H],
+ * bc [n_members][1] (H = widths[n_hidden-1]).  grad is laid out for the
+ * stacked tensors,
+ *   w1 [M][..] | b1 [M][..] | ... | wL | bL | wa [M][k*H] | ba [M][k] |
+ *   wc [M][H] | bc [M]                             (M = n_members)
+ * each segment member-major, so consecutive views of it match the stacked
+ * parameters.  Every member has its own values, advantages, GAE partials
+ * and block partials, and every decision (GAE variant, number of gradient
+ * blocks min(ceil(T*S / 64), 256)) is taken from the member's own T*S;
+ * block partials are sized by the blocks a member launches.
+ * Contract: member m's segments of grad are bit-identical to
+ * swarm_ppo_deep_epoch_grad on member m's data and parameters alone,
+ * whoever shares the launch.  Deterministic, no floating-point atomics.
+ * The limits of swarm_ppo_deep_epoch_grad (2 <= n_hidden <= 3, widths <=
+ * 128, d_in <= 32, k <= 16, T*S < 2^31) and 1 <= n_members <= 1024; outside
+ * them the calls return an error (workspace_bytes: -1) and launch nothing.
+ * workspace: device memory of at least
+ * swarm_ppo_deep_ensemble_workspace_bytes(...) bytes; a smaller one is
+ * SWARM_EINVAL and nothing is launched.  The first call of a network shape
+ * on a device must not be under stream capture (it raises the kernel's
+ * dynamic LDS limit).  The optimizer step stays the caller's.  Asynchronous
+ * on `stream`, capturable. */
+int64_t swarm_ppo_deep_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
+                                                int32_t d_in, int32_t n_hidden,
+                                                const int32_t *widths, int32_t k);
+int swarm_ppo_deep_ensemble_epoch_grad(const float *x, int32_t n_members, int32_t T, int32_t S,
+                                       int32_t d_in, const int64_t *actions,
+                                       const float *old_logp, const float *rewards,
+                                       int32_t n_hidden, const int32_t *widths,
+                                       const float *const *w, const float *const *b,
+                                       const float *wa, const float *ba, int32_t k,
+                                       const float *wc, const float *bc, float gamma,
+                                       float lambda, float clip_eps, float entropy_coef,
+                                       void *workspace, int64_t workspace_bytes, float *grad,
+                                       void *stream);
+
 /* Random Network Distillation distance (the intrinsic reward of
  * swarmrl/intrinsic_reward/random_network_distillation.py:126-143 with the
  * networks of rnd_configs.py:17-38): for every observation a < n of x

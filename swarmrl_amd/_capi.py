@@ -216,6 +216,22 @@ _SIGNATURES = {
          ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float, ctypes.c_float,
          ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P],
     ),
+    "swarm_policy_deep_ensemble_sample": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P,
+         ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P],
+    ),
+    "swarm_ppo_deep_ensemble_workspace_bytes": (
+        ctypes.c_int64,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P,
+         ctypes.c_int32],
+    ),
+    "swarm_ppo_deep_ensemble_epoch_grad": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+         ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P],
+    ),
     "swarm_ppo_profile": (ctypes.c_int, [ctypes.c_int32, _P, _P]),
     "swarm_engine_step_count": (ctypes.c_int64, [_P]),
     "swarm_rnd_distance": (

@@ -208,8 +208,14 @@ __device__ __forceinline__ void deep_stage_rows(const float* __restrict__ x, lon
 // m carries the sampling arguments (obs, n, d_in, k, keys, counters, tables,
 // outputs); its one-hidden-layer weights are not read.  K: the padded action
 // count of the sampling tail (4 or 16).
+// The body of k_policy_deep_sample: workgroup blockIdx.x of a launch over m.n
+// agents.  swarm_ensemble.cuh runs it per member on the member's slices: dp
+// then holds the stacked parameters and mi the member, whose layers start
+// mi layer sizes in (dp stays the kernel's own argument, so its arrays are
+// indexed in place; the single-model kernel passes the constant 0).
 template <int K>
-__global__ __launch_bounds__(256) void k_policy_deep_sample(MlpArgs m, DeepArgs dp) {
+__device__ __forceinline__ void deep_policy_body(const MlpArgs& m, const DeepArgs& dp,
+                                                 size_t mi) {
   __shared__ __align__(16) float act[kDeepAgents * kDeepStride];
   __shared__ float lgs[kDeepAgents * kDeepLogitRow];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -222,16 +228,19 @@ __global__ __launch_bounds__(256) void k_policy_deep_sample(MlpArgs m, DeepArgs 
   __syncthreads();
   int cols = m.d_in;
   for (int l = 0; l < dp.n_hidden; ++l) {
-    deep_layer<4>(dp.w[l], dp.b[l], dp.width[l], cols, act, kDeepStride, act, lane, wv);
-    cols = dp.width[l];
+    const int rows = dp.width[l];
+    deep_layer<4>(dp.w[l] + mi * (size_t)rows * cols, dp.b[l] + mi * (size_t)rows, rows, cols,
+                  act, kDeepStride, act, lane, wv);
+    cols = rows;
   }
   // the actor head: wave wv takes agent tile wv
   {
-    const deep_f4 z = deep_head(dp.wa, k, cols, act, lane, wv);
+    const float* __restrict__ ba = dp.ba + mi * (size_t)k;
+    const deep_f4 z = deep_head(dp.wa + mi * (size_t)k * cols, k, cols, act, lane, wv);
     const int ul = lane & 15, q = lane >> 4;
     float* lrow = lgs + (16 * wv + ul) * kDeepLogitRow + 4 * q;  // actions 4 q + reg
 #pragma unroll
-    for (int r = 0; r < 4; ++r) lrow[r] = z[r] + (4 * q + r < k ? dp.ba[4 * q + r] : 0.0f);
+    for (int r = 0; r < 4; ++r) lrow[r] = z[r] + (4 * q + r < k ? ba[4 * q + r] : 0.0f);
   }
   __syncthreads();
   if (valid) {
@@ -241,6 +250,11 @@ __global__ __launch_bounds__(256) void k_policy_deep_sample(MlpArgs m, DeepArgs 
     policy_emit<K>(m, a, lg, ctr);
   }
   advance_group_counter(m.state, a, n, tid < kDeepAgents, ctr);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void k_policy_deep_sample(MlpArgs m, DeepArgs dp) {
+  deep_policy_body<K>(m, dp, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -299,12 +313,14 @@ __host__ __device__ constexpr int deep_grads_lds_floats(bool three) {
   return 2 * kDeepAgents * kDeepXStride + (three ? 4 : 3) * kDeepAgents * kDeepStride;
 }
 
+// net and mi as in deep_policy_body (the hidden layers of member mi of a
+// stack; 0 for a single model); x, wc, bc and values are the member's own.
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_ppo_deep_values(const float* __restrict__ x, int n,
-                                                             int d, DeepArgs net,
-                                                             const float* __restrict__ wc,
-                                                             const float* __restrict__ bc,
-                                                             float* __restrict__ values) {
+__device__ __forceinline__ void deep_ppo_values_body(const float* __restrict__ x, int n, int d,
+                                                     const DeepArgs& net,
+                                                     const float* __restrict__ wc,
+                                                     const float* __restrict__ bc,
+                                                     float* __restrict__ values, size_t mi) {
   __shared__ __align__(16) float act[kDeepAgents * kDeepStride];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -313,14 +329,25 @@ __global__ __launch_bounds__(64 * NW) void k_ppo_deep_values(const float* __rest
   __syncthreads();
   int cols = d;
   for (int l = 0; l < net.n_hidden; ++l) {
-    deep_layer<NW>(net.w[l], net.b[l], net.width[l], cols, act, kDeepStride, act, lane, wv);
-    cols = net.width[l];
+    const int rows = net.width[l];
+    deep_layer<NW>(net.w[l] + mi * (size_t)rows * cols, net.b[l] + mi * (size_t)rows, rows, cols,
+                   act, kDeepStride, act, lane, wv);
+    cols = rows;
   }
   if (wv < 4) {  // the critic as a head of one row: row 0 is with lanes q = 0, reg 0
     const deep_f4 z = deep_head(wc, 1, cols, act, lane, wv);
     const long s = row0 + 16 * wv + (lane & 15);
     if ((lane >> 4) == 0 && s < n) values[s] = z[0] + bc[0];
   }
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_ppo_deep_values(const float* __restrict__ x, int n,
+                                                             int d, DeepArgs net,
+                                                             const float* __restrict__ wc,
+                                                             const float* __restrict__ bc,
+                                                             float* __restrict__ values) {
+  deep_ppo_values_body<NW>(x, n, d, net, wc, bc, values, 0);
 }
 
 // ppo_advantage_sums for a block of up to 8 waves (fixed order: thread-strided
@@ -461,11 +488,12 @@ __device__ __forceinline__ void deep_store_dw(float* out, int off_w, int off_b, 
 
 // K: the padded action count of the per-sample phase (4 or 16); L3: three
 // hidden layers (else two).  Block of 8 waves, dynamic LDS
-// deep_grads_lds_floats(L3) floats.
+// deep_grads_lds_floats(L3) floats (deep_lds).  Block blockIdx.x of
+// gridDim.x takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of the
+// p.n samples and writes row blockIdx.x of p.partial.
 template <int K, bool L3>
-__global__ __launch_bounds__(512) void k_ppo_deep_grads(DeepPpoArgs p) {
+__device__ __forceinline__ void deep_ppo_grads_body(const DeepPpoArgs& p, float* deep_lds) {
   constexpr int NW = 8;
-  extern __shared__ __align__(16) float deep_lds[];
   float* X = deep_lds;                            // [64][kDeepXStride] features
   float* gz = X + kDeepAgents * kDeepXStride;     // [64][kDeepXStride] dL/dz | dL/dV | 0
   float* g = gz + kDeepAgents * kDeepXStride;     // [64][kDeepStride] dh of the current layer
@@ -633,6 +661,12 @@ __global__ __launch_bounds__(512) void k_ppo_deep_grads(DeepPpoArgs p) {
       }
     }
   }
+}
+
+template <int K, bool L3>
+__global__ __launch_bounds__(512) void k_ppo_deep_grads(DeepPpoArgs p) {
+  extern __shared__ __align__(16) float deep_lds[];
+  deep_ppo_grads_body<K, L3>(p, deep_lds);
 }
 
 }  // namespace swarm

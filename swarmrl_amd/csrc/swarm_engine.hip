@@ -4538,6 +4538,227 @@ int swarm_ppo_ensemble_epoch_grad(const float* x, int32_t n_members, int32_t T, 
 #undef SWARM_ENS_PPO
 #undef SWARM_ENS_PPO_H
 
+// ---- ensembles of deep actor-critic MLPs (swarm_ensemble.cuh over swarm_deep.cuh)
+
+int swarm_policy_deep_ensemble_sample(const float* obs, int32_t n_members, int32_t n_per,
+                                      int32_t d_in, int32_t n_hidden, const int32_t* widths,
+                                      const float* const* w, const float* const* b,
+                                      const float* wa, const float* ba, int32_t k,
+                                      const uint64_t* seeds, uint64_t* state,
+                                      int32_t n_state_per, float explore_p, const float* f_table,
+                                      const float* t_table, int64_t* out_idx, float* out_logp,
+                                      float* out_f, float* out_t, float* out_logits,
+                                      void* stream) {
+  if (!obs || !widths || !w || !b || !wa || !ba || !seeds || !state || !f_table || !t_table ||
+      !out_idx || !out_logp || !out_f || !out_t)
+    return fail(SWARM_EINVAL, "null argument");
+  if (n_members < 1 || n_members > swarm::kEnsembleMaxMembers)
+    return fail(SWARM_ECAPACITY, "1 <= n_members <= 1024");
+  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
+  swarm::DeepEnsembleArgs e{};
+  e.dp.n_hidden = n_hidden;
+  for (int l = 0; l < n_hidden; ++l) {
+    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
+    e.dp.width[l] = widths[l];
+    e.dp.w[l] = w[l];
+    e.dp.b[l] = b[l];
+  }
+  e.dp.wa = wa;
+  e.dp.ba = ba;
+  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
+    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
+  if (n_per <= 0) return SWARM_OK;
+  if (n_state_per < (n_per + 63) / 64)
+    return fail(SWARM_EINVAL, "state needs ceil(n_per / 64) counters per member");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  e.m = swarm::MlpArgs{obs,     n_per,   d_in,    nullptr, nullptr, 0,  nullptr,
+                       nullptr, k,       0u,      0u,
+                       reinterpret_cast<unsigned long long*>(state), explore_p, f_table,
+                       t_table, out_idx, out_logp, out_f,  out_t,   out_logits};
+  e.seeds = reinterpret_cast<const unsigned long long*>(seeds);
+  e.n_state_per = n_state_per;
+  // whole blocks of 64 agents per member: one workgroup, one counter group
+  const dim3 grid((unsigned)((n_per + swarm::kDeepAgents - 1) / swarm::kDeepAgents),
+                  (unsigned)n_members);
+  if (k <= 4)
+    hipLaunchKernelGGL(swarm::k_policy_deep_ensemble_sample<4>, grid, dim3(256), 0, s, e);
+  else
+    hipLaunchKernelGGL(swarm::k_policy_deep_ensemble_sample<16>, grid, dim3(256), 0, s, e);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+namespace {
+const char* deep_ensemble_limits(int32_t M, int32_t T, int32_t S, int32_t d_in, int32_t n_hidden,
+                                 const int32_t* widths, int32_t k) {
+  if (M < 1 || M > swarm::kEnsembleMaxMembers) return "1 <= n_members <= 1024";
+  if ((long)T * S > INT32_MAX) return "T x S < 2^31 samples per member";
+  return deep_limits(d_in, n_hidden, widths, k);
+}
+
+// Member-major slices: values | adv | dv [M][n], GAE partials
+// [M][2 gae_blocks] (fp64), block partials [M][deep_ppo_blocks(n)][size] --
+// sized by the blocks a member launches.
+DeepPpoWorkspace deep_ppo_ensemble_workspace(size_t M, long n, long S, int size) {
+  DeepPpoWorkspace w;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  w.values = 0;
+  w.adv = up(w.values + M * (size_t)n * 4);
+  w.dv = up(w.adv + M * (size_t)n * 4);
+  w.spart = up(w.dv + M * (size_t)n * 4);
+  w.partial = up(w.spart + M * (size_t)((S + 255) / 256) * 2 * sizeof(double));
+  w.total = up(w.partial + M * (size_t)deep_ppo_blocks(n) * (size_t)size * 4);
+  return w;
+}
+}  // namespace
+
+int64_t swarm_ppo_deep_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
+                                                int32_t d_in, int32_t n_hidden,
+                                                const int32_t* widths, int32_t k) {
+  if (T < 1 || S < 1 || !widths ||
+      deep_ensemble_limits(n_members, T, S, d_in, n_hidden, widths, k))
+    return -1;
+  return (int64_t)deep_ppo_ensemble_workspace((size_t)n_members, (long)T * S, S,
+                                              deep_ppo_grad_size(d_in, n_hidden, widths, k))
+      .total;
+}
+
+int swarm_ppo_deep_ensemble_epoch_grad(const float* x, int32_t n_members, int32_t T, int32_t S,
+                                       int32_t d_in, const int64_t* actions,
+                                       const float* old_logp, const float* rewards,
+                                       int32_t n_hidden, const int32_t* widths,
+                                       const float* const* w, const float* const* b,
+                                       const float* wa, const float* ba, int32_t k,
+                                       const float* wc, const float* bc, float gamma,
+                                       float lambda, float clip_eps, float entropy_coef,
+                                       void* workspace, int64_t workspace_bytes, float* grad,
+                                       void* stream) {
+  if (!x || !actions || !old_logp || !rewards || !widths || !w || !b || !wa || !ba || !wc ||
+      !bc || !workspace || !grad)
+    return fail(SWARM_EINVAL, "null argument");
+  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
+  if (const char* why = deep_ensemble_limits(n_members, T, S, d_in, n_hidden, widths, k))
+    return fail(SWARM_ECAPACITY, why);
+  swarm::DeepPpoEnsembleArgs a{};
+  swarm::DeepPpoArgs& p = a.p;
+  p.net.n_hidden = n_hidden;
+  int off = 0, prev = d_in, nseg = 0;
+  for (int l = 0; l < n_hidden; ++l) {
+    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
+    p.net.width[l] = widths[l];
+    p.net.w[l] = w[l];
+    p.net.b[l] = b[l];
+    p.off_w[l] = off;
+    off += widths[l] * prev;
+    p.off_b[l] = off;
+    off += widths[l];
+    a.seg[nseg++] = widths[l] * prev;
+    a.seg[nseg++] = widths[l];
+    prev = widths[l];
+  }
+  p.net.wa = wa;
+  p.net.ba = ba;
+  p.off_wa = off;
+  off += k * prev;
+  p.off_ba = off;
+  off += k;
+  p.off_wc = off;
+  off += prev;
+  p.off_bc = off;
+  p.size = off + 1;
+  a.seg[nseg++] = k * prev;
+  a.seg[nseg++] = k;
+  a.seg[nseg++] = prev;
+  a.seg[nseg++] = 1;
+  const int n = T * S;
+  const size_t M = (size_t)n_members;
+  const DeepPpoWorkspace ws = deep_ppo_ensemble_workspace(M, n, S, p.size);
+  if (workspace_bytes < (int64_t)ws.total)
+    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_deep_ensemble_workspace_bytes");
+  char* base = static_cast<char*>(workspace);
+  float* adv = reinterpret_cast<float*>(base + ws.adv);
+  float* dv = reinterpret_cast<float*>(base + ws.dv);
+  double* spart = reinterpret_cast<double*>(base + ws.spart);
+  const int gae_blocks = (S + 255) / 256;
+  // every decision from the member's own n, as swarm_ppo_deep_epoch_grad takes it
+  const unsigned tiles = (unsigned)(((long)n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
+  const int blocks = deep_ppo_blocks(n);
+  p.x = x;
+  p.n = n;
+  p.d = d_in;
+  p.k = k;
+  p.wc = wc;
+  p.bc = bc;
+  p.actions = actions;
+  p.old_logp = old_logp;
+  p.adv = adv;
+  p.dvalue = dv;
+  p.gae_part = spart;
+  p.n_part = gae_blocks;
+  p.clip_eps = clip_eps;
+  p.c_ent = entropy_coef;
+  p.partial = reinterpret_cast<float*>(base + ws.partial);
+  a.values = reinterpret_cast<float*>(base + ws.values);
+  a.members = n_members;
+  a.blocks = blocks;
+  a.grad = grad;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned Mu = (unsigned)n_members;
+  hipLaunchKernelGGL(swarm::k_ppo_deep_ensemble_values<8>, dim3(tiles, Mu), dim3(512), 0, s, a);
+  // k_ppo_ensemble_gae without pack workgroups (its grid is the GAE blocks:
+  // no parameter table, so the one-layer weights stay null)
+  swarm::PpoEnsembleArgs g{};
+  g.rewards = rewards;
+  g.T = T;
+  g.S = S;
+  g.n = n;
+  g.members = n_members;
+  g.gamma = gamma;
+  g.lambda = lambda;
+  g.values = a.values;
+  g.adv = adv;
+  g.dv = dv;
+  g.spart = spart;
+  g.gae_blocks = gae_blocks;
+  if (T <= 32)
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<32, 1, 4>), dim3((unsigned)gae_blocks, Mu),
+                       dim3(256), 0, s, g);
+  else
+    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<0, 1, 4>), dim3((unsigned)gae_blocks, Mu),
+                       dim3(256), 0, s, g);
+  const bool three = n_hidden == 3;
+  const int lds = swarm::deep_grads_lds_floats(three) * (int)sizeof(float);
+  int dev = -1;
+  HIP_TRY(hipGetDevice(&dev));
+#define SWARM_DEEP_ENS_GRADS(KK, LL)                                                            \
+  do {                                                                                          \
+    /* more than 64 KB of dynamic LDS: allowed once per device (the first call */               \
+    /* of a size is never under capture: callers size the workspace eagerly) */                 \
+    static bool allowed[64] = {};                                                               \
+    if (dev < 0 || dev >= 64 || !allowed[dev]) {                                                \
+      HIP_TRY(hipFuncSetAttribute(                                                              \
+          reinterpret_cast<const void*>(&swarm::k_ppo_deep_ensemble_grads<KK, LL>),             \
+          hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                    \
+      if (dev >= 0 && dev < 64) allowed[dev] = true;                                            \
+    }                                                                                           \
+    hipLaunchKernelGGL((swarm::k_ppo_deep_ensemble_grads<KK, LL>),                              \
+                       dim3((unsigned)blocks, Mu), dim3(512), (size_t)lds, s, a);               \
+  } while (0)
+  if (k <= 4 && !three)
+    SWARM_DEEP_ENS_GRADS(4, false);
+  else if (k <= 4)
+    SWARM_DEEP_ENS_GRADS(4, true);
+  else if (!three)
+    SWARM_DEEP_ENS_GRADS(16, false);
+  else
+    SWARM_DEEP_ENS_GRADS(16, true);
+#undef SWARM_DEEP_ENS_GRADS
+  hipLaunchKernelGGL(swarm::k_ppo_deep_ensemble_reduce,
+                     dim3((unsigned)((p.size + 63) / 64), Mu), dim3(1024), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
 int swarm_neighbor_reduce(const double* pos, const double* dir, const double* vel,
                           const int32_t* types, int32_t n_envs, int32_t n,
                           const int32_t* agent_idx, int32_t n_agents, uint32_t cand_type_mask,

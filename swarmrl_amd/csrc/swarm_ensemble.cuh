@@ -8,7 +8,8 @@
 // keep the meaning they have in the single-model kernels.  Each kernel
 // offsets its pointers to the member's slices and runs the single-model body
 // (policy_body of swarm_policy.cuh, the ppo_*_body functions of
-// swarm_ppo.cuh) on them: the same instructions in the same order on the
+// swarm_ppo.cuh, the deep_*_body functions of swarm_deep.cuh) on them: the
+// same instructions in the same order on the
 // same values, so a member's results are bit-identical to the single-model
 // call on its slice alone, whoever shares the launch.  A workgroup serves
 // one member only; sample, agent and counter-group indices are local to the
@@ -18,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "swarm_deep.cuh"
 #include "swarm_policy.cuh"
 #include "swarm_ppo.cuh"
 
@@ -140,6 +142,121 @@ __global__ __launch_bounds__(1024) void k_ppo_ensemble_reduce(PpoEnsembleArgs a)
     }
     grad[M * lo + mi * len + (p - lo)] = g;
   });
+}
+
+// ---------------------------------------------------------------------------
+// Ensembles of deep actor-critic MLPs (2 or 3 hidden layers, swarm_deep.cuh).
+
+// Member mi's hidden layers and actor head for the gradient kernel, which
+// indexes them with constants: every stacked tensor at member
+// stride ([M][width[l]][width[l - 1]], [M][width[l]], wa [M][k][width[L - 1]],
+// ba [M][k]).  Returns the last hidden width.
+__device__ __forceinline__ int deep_member_net(DeepArgs& net, size_t mi, int d_in, int k) {
+  int prev = d_in;
+#pragma unroll
+  for (int l = 0; l < kDeepMaxLayers; ++l) {
+    if (l < net.n_hidden) {
+      net.w[l] += mi * (size_t)net.width[l] * prev;
+      net.b[l] += mi * (size_t)net.width[l];
+      prev = net.width[l];
+    }
+  }
+  net.wa += mi * (size_t)k * prev;
+  net.ba += mi * (size_t)k;
+  return prev;
+}
+
+// swarm_policy_deep_ensemble_sample: obs [M][n_per][d_in], seeds [M] (device),
+// state [M][n_state_per], outputs [M * n_per].  Grid (ceil(n_per / 64), M):
+// one workgroup is one counter group of one member.
+struct DeepEnsembleArgs {
+  MlpArgs m;    // member 0's pointers; n = n_per; the keys are read from seeds
+  DeepArgs dp;  // member 0's pointers
+  const unsigned long long* seeds;
+  int n_state_per;
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void k_policy_deep_ensemble_sample(DeepEnsembleArgs e) {
+  const size_t mi = blockIdx.y;
+  MlpArgs m = e.m;
+  const size_t n = (size_t)m.n;
+  m.obs += mi * n * m.d_in;
+  const unsigned long long seed = e.seeds[mi];
+  m.key0 = (uint32_t)seed;
+  m.key1 = (uint32_t)(seed >> 32);
+  m.state += mi * (size_t)e.n_state_per;
+  m.out_idx += mi * n;
+  m.out_logp += mi * n;
+  m.out_f += mi * n;
+  m.out_t += mi * n;
+  if (m.out_logits) m.out_logits += mi * n * m.k;
+  deep_policy_body<K>(m, e.dp, mi);  // the member's layers of the stack e.dp
+}
+
+// swarm_ppo_deep_ensemble_epoch_grad: p holds member 0's pointers (data,
+// stacked parameters, workspace slices) and the single-model gradient layout;
+// the strides follow from the sizes.  The GAE launch is k_ppo_ensemble_gae
+// without pack workgroups.  The stacked gradient layout is
+// w1 [M][..] | b1 [M][..] | ... | wL | bL | wa | ba | wc | bc, each segment
+// member-major: seg[t] is the single-model size of tensor t (2 L + 4 of them).
+struct DeepPpoEnsembleArgs {
+  DeepPpoArgs p;
+  float* values;  // [M][n]
+  int members, blocks;  // blocks: grads blocks (= partial rows) per member
+  int seg[2 * kDeepMaxLayers + 4];
+  float* grad;
+};
+
+__device__ __forceinline__ DeepPpoArgs deep_ppo_member(const DeepPpoEnsembleArgs& a, size_t mi) {
+  DeepPpoArgs p = a.p;
+  const size_t n = (size_t)p.n;
+  p.x += mi * n * p.d;
+  const int last = deep_member_net(p.net, mi, p.d, p.k);
+  p.wc += mi * (size_t)last;
+  p.bc += mi;
+  p.actions += mi * n;
+  p.old_logp += mi * n;
+  p.adv += mi * n;
+  p.dvalue += mi * n;
+  p.gae_part += mi * 2 * (size_t)p.n_part;
+  p.partial += mi * (size_t)a.blocks * p.size;
+  return p;
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_ppo_deep_ensemble_values(DeepPpoEnsembleArgs a) {
+  // a.p.net stays in place (its arrays are indexed by the layer loop)
+  const size_t mi = blockIdx.y, n = (size_t)a.p.n;
+  const int last = a.p.net.width[a.p.net.n_hidden - 1];
+  deep_ppo_values_body<NW>(a.p.x + mi * n * a.p.d, a.p.n, a.p.d, a.p.net,
+                           a.p.wc + mi * (size_t)last, a.p.bc + mi, a.values + mi * n, mi);
+}
+
+template <int K, bool L3>
+__global__ __launch_bounds__(512) void k_ppo_deep_ensemble_grads(DeepPpoEnsembleArgs a) {
+  extern __shared__ __align__(16) float deep_lds[];
+  const DeepPpoArgs p = deep_ppo_member(a, blockIdx.y);
+  deep_ppo_grads_body<K, L3>(p, deep_lds);
+}
+
+// Member blockIdx.y's block partials -> its rows of the stacked gradient.
+__global__ __launch_bounds__(1024) void k_ppo_deep_ensemble_reduce(DeepPpoEnsembleArgs a) {
+  const size_t mi = blockIdx.y, M = (size_t)a.members;
+  const int size = a.p.size;
+  float* grad = a.grad;
+  ppo_reduce_body(a.p.partial + mi * (size_t)a.blocks * size, a.blocks, size,
+                  [&](int p, float g) {
+                    int lo = 0, len = a.seg[0];  // p's tensor: parameters [lo, lo + len)
+#pragma unroll
+                    for (int t = 1; t < 2 * kDeepMaxLayers + 4; ++t) {
+                      if (p >= lo + len) {
+                        lo += len;
+                        len = a.seg[t];
+                      }
+                    }
+                    grad[M * lo + mi * len + (p - lo)] = g;
+                  });
 }
 
 }  // namespace swarm

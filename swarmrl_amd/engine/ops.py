@@ -641,13 +641,121 @@ def policy_ensemble_sample(obs: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor
     return idx, logp, f, t
 
 
-def ppo_ensemble_grad_size(M: int, d_in: int, hidden: int, k: int) -> int:
-    return M * (hidden * d_in + hidden + k * hidden + k + hidden + 1)
+def policy_deep_ensemble_sample(obs: torch.Tensor, ws, bs, wa: torch.Tensor, ba: torch.Tensor,
+                                seeds: torch.Tensor, state: torch.Tensor, explore_p: float,
+                                f_table: torch.Tensor, t_table: torch.Tensor,
+                                want_logits: bool = False, out=None):
+    """
+    The rollout policy of M independent deep actor-critic MLPs in one kernel
+    (swarm_policy_deep_ensemble_sample).  obs [M * n_per, d_in] (or [M, n_per,
+    d_in]) fp32 device, member m owning rows [m * n_per, (m + 1) * n_per);
+    ws / bs the 2 or 3 stacked hidden torch Linear weights [M, h_l, h_(l-1)]
+    and biases [M, h_l] in order, wa [M, k, h_L] / ba [M, k] the actor head;
+    seeds [M] int64 device, state [M, n_state_per] int64 device counters with
+    n_state_per >= ceil(n_per / 64).  Member m's results and advanced counters
+    are bit-identical to policy_deep_sample on its slice with seeds[m] and
+    state[m].  out: (idx, log_prob, f_swim, torque_z) to write into.  Returns
+    (idx, log_prob, f_swim, torque_z[, logits]), each [M * n_per].
+    """
+    ws, bs = list(ws), list(bs)
+    if len(ws) != len(bs) or not ws:
+        raise ValueError("one bias per hidden layer")
+    M, d_in = int(ws[0].shape[0]), int(ws[0].shape[2])
+    k = int(wa.shape[1])
+    if obs.dim() != 2 or obs.shape[1] != d_in:
+        obs = obs.reshape(-1, d_in)
+    if obs.dtype != torch.float32:
+        obs = obs.to(torch.float32)
+    obs = obs.contiguous()
+    n = obs.shape[0]
+    if n % M != 0:
+        raise ValueError(f"{n} observations do not divide among {M} ensemble members")
+    # the kernel indexes the stacked tensors by member: their shapes are its bounds
+    _check_deep_stack(M, d_in, ws, bs, wa, ba)
+    if state.dim() != 2 or state.shape[0] != M or not state.is_contiguous():
+        raise ValueError("state must be a contiguous [M, n_state_per] tensor")
+    if seeds.shape != (M,) or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+        raise ValueError("seeds must be a contiguous int64 tensor of M entries")
+    dev = obs.device
+    if out is not None:
+        idx, logp, f, t = out
+        if (idx.dtype != torch.int64 or not all(
+                o.numel() == n and o.is_contiguous() for o in out)
+                or not (logp.dtype == f.dtype == t.dtype == torch.float32)):
+            raise ValueError("out must be contiguous (int64, fp32, fp32, fp32) tensors of "
+                             "M * n_per entries")
+    else:
+        idx = torch.empty(n, dtype=torch.int64, device=dev)
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        f = torch.empty(n, dtype=torch.float32, device=dev)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+    logits = torch.empty(n, k, dtype=torch.float32, device=dev) if want_logits else None
+    widths = (ctypes.c_int32 * len(ws))(*(int(w.shape[1]) for w in ws))
+    wp, bp = _pointer_array(ws), _pointer_array(bs)  # host arrays, read during the call
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().swarm_policy_deep_ensemble_sample(
+        obs.data_ptr(), M, n // M, d_in, len(ws), ctypes.cast(widths, ctypes.c_void_p),
+        ctypes.cast(wp, ctypes.c_void_p), ctypes.cast(bp, ctypes.c_void_p), wa.data_ptr(),
+        ba.data_ptr(), k, seeds.data_ptr(), state.data_ptr(), state.shape[1],
+        ctypes.c_float(explore_p), f_table.data_ptr(), t_table.data_ptr(), idx.data_ptr(),
+        logp.data_ptr(), f.data_ptr(), t.data_ptr(),
+        logits.data_ptr() if want_logits else None, ctypes.c_void_p(stream)))
+    if want_logits:
+        return idx, logp, f, t, logits
+    return idx, logp, f, t
 
 
-def ppo_ensemble_workspace_bytes(M: int, T: int, S: int, d_in: int, hidden: int, k: int) -> int:
-    """swarm_ppo_ensemble_workspace_bytes; raises beyond the kernels' limits."""
-    nbytes = int(_capi.lib().swarm_ppo_ensemble_workspace_bytes(M, T, S, d_in, hidden, k))
+def _check_deep_stack(M, d_in, ws, bs, wa, ba, wc=None, bc=None):
+    """Raise unless the stacked deep layers are contiguous fp32 [M, ...]
+    tensors whose shapes chain from d_in (the kernels' bounds)."""
+    prev = d_in
+    ok = True
+    for w, b in zip(ws, bs):
+        ok = ok and w.dim() == 3 and tuple(w.shape) == (M, w.shape[1], prev)
+        ok = ok and tuple(b.shape) == (M, w.shape[1])
+        prev = int(w.shape[1]) if w.dim() == 3 else prev
+    k = wa.shape[1] if wa.dim() == 3 else -1
+    ok = ok and tuple(wa.shape) == (M, k, prev) and tuple(ba.shape) == (M, k)
+    flat = [*ws, *bs, wa, ba]
+    if wc is not None:
+        ok = ok and tuple(wc.shape) == (M, 1, prev) and tuple(bc.shape) == (M, 1)
+        flat += [wc, bc]
+    ok = ok and all(t.is_contiguous() and t.dtype == torch.float32 for t in flat)
+    if not ok:
+        raise ValueError("stacked parameters must be contiguous fp32 [M, ...] tensors")
+
+
+def _hidden_widths(hidden):
+    """None for the one-hidden-layer network (an int), else the widths."""
+    if isinstance(hidden, (int, np.integer)):
+        return None
+    return [int(h) for h in hidden]
+
+
+def ppo_ensemble_grad_size(M: int, d_in: int, hidden, k: int) -> int:
+    """Floats of the stacked gradient.  hidden: the width of the
+    one-hidden-layer network, or the sequence of widths of the deep one."""
+    widths = _hidden_widths(hidden)
+    if widths is None:
+        return M * (hidden * d_in + hidden + k * hidden + k + hidden + 1)
+    size, prev = 0, d_in
+    for h in widths:
+        size += h * prev + h
+        prev = h
+    return M * (size + k * prev + k + prev + 1)
+
+
+def ppo_ensemble_workspace_bytes(M: int, T: int, S: int, d_in: int, hidden, k: int) -> int:
+    """swarm_ppo_ensemble_workspace_bytes, or for a sequence of hidden widths
+    swarm_ppo_deep_ensemble_workspace_bytes; raises beyond the kernels'
+    limits."""
+    widths = _hidden_widths(hidden)
+    if widths is None:
+        nbytes = int(_capi.lib().swarm_ppo_ensemble_workspace_bytes(M, T, S, d_in, hidden, k))
+    else:
+        arr = (ctypes.c_int32 * max(len(widths), 1))(*widths)
+        nbytes = int(_capi.lib().swarm_ppo_deep_ensemble_workspace_bytes(
+            M, T, S, d_in, len(widths), ctypes.cast(arr, ctypes.c_void_p), k))
     if nbytes < 0:
         raise ValueError("sizes beyond the ensemble PPO kernels' limits")
     return nbytes
@@ -669,11 +777,18 @@ def ppo_ensemble_epoch_grad(features: torch.Tensor, actions: torch.Tensor,
     ppo_epoch_grad on its slices.  Inputs already fp32 / int64 and contiguous
     are used in place (the launches can be graph-captured).  workspaces: the
     caller's cache, as in ppo_epoch_grad; workspace: an explicit uint8 device
-    buffer instead (its size is checked by the library).
+    buffer instead (its size is checked by the library).  More than six
+    layers: the stacked deep MLP (w1, b1, ..., wL, bL, wa, ba, wc, bc) through
+    swarm_ppo_deep_ensemble_epoch_grad, the gradient in that order and member
+    m's part bit-identical to the deep ppo_epoch_grad on its slices.
     """
     M, T, S = actions.shape
     x = features.reshape(M, T * S, -1).to(torch.float32).contiguous()
     d_in = x.shape[2]
+    if len(layers) > 6:
+        return _ppo_deep_ensemble_epoch_grad(x, actions, old_logp, rewards, layers, gamma,
+                                             lambda_, clip_eps, entropy_coef, out, workspaces,
+                                             workspace)
     w1, b1, wa, ba, wc, bc = layers
     hidden, k = w1.shape[1], wa.shape[1]
     # the kernels index the stacked tensors by member: their shapes are the bounds
@@ -706,6 +821,52 @@ def ppo_ensemble_epoch_grad(features: torch.Tensor, actions: torch.Tensor,
     _capi.check(lib.swarm_ppo_ensemble_epoch_grad(
         x.data_ptr(), M, T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(),
         w1.data_ptr(), b1.data_ptr(), hidden, wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
+        bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
+        ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
+        ctypes.c_void_p(stream)))
+    return grad
+
+
+def _ppo_deep_ensemble_epoch_grad(x, actions, old_logp, rewards, layers, gamma, lambda_,
+                                  clip_eps, entropy_coef, out, workspaces, workspace):
+    """ppo_ensemble_epoch_grad for the stacked deep MLP
+    (swarm_ppo_deep_ensemble_epoch_grad): x [M, T * S, d] fp32 contiguous."""
+    M, T, S = actions.shape
+    d_in = int(x.shape[2])
+    hidden = layers[:-4]
+    wa, ba, wc, bc = layers[-4:]
+    ws_, bs_ = list(hidden[0::2]), list(hidden[1::2])
+    # the kernels index the stacked tensors by member: their shapes are the bounds
+    _check_deep_stack(M, d_in, ws_, bs_, wa, ba, wc, bc)
+    if old_logp.shape != actions.shape or rewards.shape != actions.shape:
+        raise ValueError("actions, old_logp and rewards must all be [M, T, S]")
+    k = int(wa.shape[1])
+    widths = [int(w.shape[1]) for w in ws_]
+    dev = x.device
+    if workspace is not None:
+        ws, nbytes = workspace, int(workspace.numel() * workspace.element_size())
+    else:
+        nbytes = ppo_ensemble_workspace_bytes(M, T, S, d_in, widths, k)
+        key = ("ppo_deep_ensemble", dev.index or 0, nbytes)
+        ws = workspaces.get(key) if workspaces is not None else None
+        if ws is None:
+            ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            if workspaces is not None:
+                workspaces[key] = ws
+    size = ppo_ensemble_grad_size(M, d_in, widths, k)
+    grad = out if out is not None else torch.empty(size, dtype=torch.float32, device=dev)
+    if grad.numel() != size or grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 tensor of the gradient's size")
+    acts = actions.to(torch.int64).contiguous()
+    olp = old_logp.to(torch.float32).contiguous()
+    rew = rewards.to(torch.float32).contiguous()
+    warr = (ctypes.c_int32 * len(widths))(*widths)
+    wp, bp = _pointer_array(ws_), _pointer_array(bs_)  # host arrays, read during the call
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().swarm_ppo_deep_ensemble_epoch_grad(
+        x.data_ptr(), M, T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(), len(ws_),
+        ctypes.cast(warr, ctypes.c_void_p), ctypes.cast(wp, ctypes.c_void_p),
+        ctypes.cast(bp, ctypes.c_void_p), wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
         bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
         ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
         ctypes.c_void_p(stream)))

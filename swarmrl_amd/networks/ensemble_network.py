@@ -11,6 +11,12 @@ are bit-identical to the single-model kernels on its slice, so a member
 trained in an ensemble is the model it would have been trained alone with
 the same seed and data.  One elementwise Adam over the stacked tensors is N
 independent Adams.
+
+EnsembleDeepActorCriticMLP is the same for DeepActorCriticMLP members (2 L + 4
+stacked parameters; swarm_policy_deep_ensemble_sample and
+swarm_ppo_deep_ensemble_epoch_grad for L = 2 or 3 within the deep kernels'
+limits), and EnsembleTorchModel.select_members is the selection step of a
+genetic routine (training_routines/genetic.py).
 """
 
 import os
@@ -20,7 +26,8 @@ import torch
 from torch import nn
 
 from swarmrl_amd.exploration_policies.random_exploration import RandomExploration
-from swarmrl_amd.networks.torch_network import ActorCriticMLP
+from swarmrl_amd.networks.torch_network import (ActorCriticMLP, DeepActorCriticMLP,
+                                                deep_mlp_within_limits)
 from swarmrl_amd.sampling_strategies.gumbel_distribution import GumbelDistribution
 
 _NAMES = ("hidden.weight", "hidden.bias", "actor.weight", "actor.bias", "critic.weight",
@@ -121,10 +128,129 @@ class EnsembleActorCriticMLP(nn.Module):
                 dst.copy_(torch.stack([m.ppo_layers()[i].detach() for m in fresh]))
 
 
+def _deep_names(n_hidden: int):
+    names = []
+    for l in range(n_hidden):
+        names += [f"layers.{l}.weight", f"layers.{l}.bias"]
+    return (*names, "actor.weight", "actor.bias", "critic.weight", "critic.bias")
+
+
+def _deep_ppo_layers(module: DeepActorCriticMLP):
+    """(w1, b1, ..., wL, bL, wa, ba, wc, bc) of a DeepActorCriticMLP."""
+    ws, bs, wa, ba, wc, bc = module.deep_layers()
+    return (*(t for pair in zip(ws, bs) for t in pair), wa, ba, wc, bc)
+
+
+class EnsembleDeepActorCriticMLP(nn.Module):
+    """n_members independent DeepActorCriticMLPs (L = len(hidden) hidden ReLU
+    layers, then {Dense(n_actions) logits, Dense(1) value}) as 2 L + 4
+    stacked parameters in torch Linear layouts: w_l [M, h_l, h_(l-1)],
+    b_l [M, h_l] (h_0 = input_dim), wa [M, k, h_L], ba [M, k],
+    wc [M, 1, h_L], bc [M, 1].  Member m is initialised exactly as the m-th
+    DeepActorCriticMLP constructed in order under the current torch RNG."""
+
+    def __init__(self, n_members: int, input_dim: int, n_actions: int = 4, hidden=(128, 128)):
+        super().__init__()
+        if n_members < 1:
+            raise ValueError("an ensemble needs at least one member")
+        self.n_members = int(n_members)
+        self.input_dim, self.n_actions = int(input_dim), int(n_actions)
+        self.hidden_widths = tuple(int(h) for h in hidden)
+        members = [DeepActorCriticMLP(input_dim, n_actions, self.hidden_widths)
+                   for _ in range(self.n_members)]
+        self._stack(members)
+
+    def _stack(self, members):
+        per_member = [_deep_ppo_layers(m) for m in members]
+        n_hidden = len(self.hidden_widths)
+        names = [n for l in range(n_hidden) for n in (f"w{l + 1}", f"b{l + 1}")]
+        names += ["wa", "ba", "wc", "bc"]
+        for i, name in enumerate(names):  # registered in the order of ppo_layers()
+            stacked = torch.stack([layers[i].detach() for layers in per_member])
+            setattr(self, name, nn.Parameter(stacked.contiguous()))
+        self._layer_names = tuple(names)
+
+    @classmethod
+    def from_members(cls, members):
+        """The ensemble whose member m is a copy of members[m]."""
+        members = list(members)
+        first = members[0]
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.n_members = len(members)
+        self.input_dim = int(first.layers[0].in_features)
+        self.n_actions = int(first.actor.out_features)
+        self.hidden_widths = tuple(int(layer.out_features) for layer in first.layers)
+        shapes = [tuple(t.shape) for t in _deep_ppo_layers(first)]
+        for m in members:
+            if [tuple(t.shape) for t in _deep_ppo_layers(m)] != shapes:
+                raise ValueError("ensemble members must have the same layer sizes")
+        self._stack(members)
+        return self
+
+    def ppo_layers(self):
+        """The stacked (w1, b1, ..., wL, bL, wa, ba, wc, bc), the order of
+        the ensemble PPO gradient (swarm_ppo_deep_ensemble_epoch_grad)."""
+        return tuple(getattr(self, name) for name in self._layer_names)
+
+    def rollout_layers(self):
+        """The stacked (ws, bs, wa, ba) of the actor path
+        (swarm_policy_deep_ensemble_sample)."""
+        layers = self.ppo_layers()
+        return (list(layers[0:-4:2]), list(layers[1:-4:2]), layers[-4], layers[-3])
+
+    def member(self, m: int) -> DeepActorCriticMLP:
+        """A copy of member m as a stock DeepActorCriticMLP."""
+        net = DeepActorCriticMLP(self.input_dim, self.n_actions, self.hidden_widths)
+        net.to(self.wa.device)
+        with torch.no_grad():
+            for dst, src in zip(_deep_ppo_layers(net), self.ppo_layers()):
+                dst.copy_(src[m])
+        return net
+
+    def set_member(self, m: int, module: DeepActorCriticMLP):
+        """Overwrite member m's weights with the module's."""
+        with torch.no_grad():
+            for dst, src in zip(self.ppo_layers(), _deep_ppo_layers(module)):
+                dst[m].copy_(src)
+
+    def member_state_dict(self, m: int) -> dict:
+        """Member m's weights under DeepActorCriticMLP's state-dict names."""
+        return {name: t[m].detach().clone()
+                for name, t in zip(_deep_names(len(self.hidden_widths)), self.ppo_layers())}
+
+    def forward(self, x):
+        """x [M, n, d] -> (logits [M, n, k], values [M, n, 1]) by batched
+        matmul (the torch path; the kernels' reference in the tests), the
+        products and bias adds of the members' Linear layers in their order;
+        the value head in the form of EnsembleActorCriticMLP.forward."""
+        layers = self.ppo_layers()
+        h = x
+        for w, b in zip(layers[0:-4:2], layers[1:-4:2]):
+            h = torch.relu(torch.bmm(h, w.transpose(1, 2)) + b.unsqueeze(1))
+        wa, ba, wc, bc = layers[-4:]
+        logits = torch.bmm(h, wa.transpose(1, 2)) + ba.unsqueeze(1)
+        values = torch.bmm(wc, h.transpose(1, 2)).transpose(1, 2) + bc.unsqueeze(1)
+        return logits, values
+
+    def reset_parameters(self):
+        """Fresh members, drawn in order from the current torch RNG."""
+        fresh = [_deep_ppo_layers(DeepActorCriticMLP(self.input_dim, self.n_actions,
+                                                     self.hidden_widths))
+                 for _ in range(self.n_members)]
+        with torch.no_grad():
+            for i, dst in enumerate(self.ppo_layers()):
+                dst.copy_(torch.stack([layers[i].detach() for layers in fresh]))
+
+
+def _is_deep(model) -> bool:
+    return hasattr(model, "hidden_widths")
+
+
 class EnsembleTorchModel:
     """The TorchModel surface the agent and the loss use, for an
-    EnsembleActorCriticMLP.  The flat batch [E * A, d] an agent builds is
-    member-major: with E envs and M members, member m owns envs
+    EnsembleActorCriticMLP or an EnsembleDeepActorCriticMLP.  The flat batch
+    [E * A, d] an agent builds is member-major: with E envs and M members, member m owns envs
     [m E/M, (m + 1) E/M), so rows [m n_per, (m + 1) n_per), n_per = (E/M) A."""
 
     # the one-launch observable + policy and the ride-along build stay
@@ -133,7 +259,7 @@ class EnsembleTorchModel:
 
     def __init__(
         self,
-        torch_model: EnsembleActorCriticMLP,
+        torch_model: nn.Module,
         input_shape: tuple = None,
         optimizer=None,
         exploration_policy=RandomExploration(probability=0.0),
@@ -214,7 +340,8 @@ class EnsembleTorchModel:
     def fused_sampling_ok(self, observables) -> bool:
         """The one-kernel ensemble policy applies: stock Gumbel sampling and
         random exploration, device tensors and parameters, sizes within
-        swarm_policy_ensemble_sample's limits."""
+        swarm_policy_ensemble_sample's limits (a deep ensemble:
+        swarm_policy_deep_ensemble_sample's)."""
         if os.environ.get("SWARMRL_AMD_FUSED_ENSEMBLE", "1") == "0":
             return False
         if not (isinstance(observables, torch.Tensor) and observables.is_cuda
@@ -222,16 +349,20 @@ class EnsembleTorchModel:
                 and type(self.exploration_policy) is RandomExploration):
             return False
         m = self.model
-        return (m.w1.is_cuda and m.input_dim <= 16 and m.hidden_units <= 256
-                and m.n_actions <= 16 and self.n_members <= 1024
+        if _is_deep(m):
+            sizes_ok = deep_mlp_within_limits(m.input_dim, m.hidden_widths, m.n_actions)
+        else:
+            sizes_ok = m.input_dim <= 16 and m.hidden_units <= 256 and m.n_actions <= 16
+        return (m.wa.is_cuda and sizes_ok and self.n_members <= 1024
                 and observables.shape[0] % self.n_members == 0)
 
     @torch.no_grad()
     def compute_action_fused(self, observables: torch.Tensor, f_table: torch.Tensor,
                              t_table: torch.Tensor):
         """Every member's compute_action + action-table lookup in one launch
-        (swarm_policy_ensemble_sample): (indices, log_probs, f_swim,
-        torque_z) for the flat member-major batch."""
+        (swarm_policy_ensemble_sample, or swarm_policy_deep_ensemble_sample
+        for a deep ensemble): (indices, log_probs, f_swim, torque_z) for the
+        flat member-major batch."""
         from swarmrl_amd.engine import ops
 
         obs = observables.to(torch.float32)
@@ -242,8 +373,10 @@ class EnsembleTorchModel:
         n_per = obs.shape[0] // self.n_members
         self._member_counters(n_per, obs.device)
         p = float(self.exploration_policy.probability)
-        return ops.policy_ensemble_sample(obs, *self.model.rollout_layers(), self._seeds,
-                                          self._fused_state, p, f_table, t_table)
+        sample = ops.policy_deep_ensemble_sample if _is_deep(self.model) \
+            else ops.policy_ensemble_sample
+        return sample(obs, *self.model.rollout_layers(), self._seeds, self._fused_state, p,
+                      f_table, t_table)
 
     def _member_counters(self, n_per: int, device):
         """The seeds on the device and [M, ceil(n_per / 64)] call counters
@@ -267,19 +400,25 @@ class EnsembleTorchModel:
     def ppo_layers(self, d_in: int):
         """The stacked layers when the fused ensemble PPO gradient applies
         (fp32 contiguous device parameters within
-        swarm_ppo_ensemble_epoch_grad's limits), else None."""
+        swarm_ppo_ensemble_epoch_grad's limits, or for a deep ensemble
+        swarm_ppo_deep_ensemble_epoch_grad's), else None."""
         if self.optimizer is None:
             return None
         layers = self.model.ppo_layers()
         ok = all(t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() for t in layers)
         ok = ok and self.model.input_dim == d_in and d_in <= 32
-        ok = ok and self.model.hidden_units <= 256 and self.model.n_actions <= 16
+        if _is_deep(self.model):
+            ok = ok and deep_mlp_within_limits(d_in, self.model.hidden_widths,
+                                               self.model.n_actions)
+        else:
+            ok = ok and self.model.hidden_units <= 256 and self.model.n_actions <= 16
         ok = ok and self.n_members <= 1024
         return layers if ok else None
 
     def apply_gradients(self, layers, flat_grad: torch.Tensor):
         """One optimizer step with the gradient given as the concatenation of
-        the stacked layers' gradients (swarm_ppo_ensemble_epoch_grad)."""
+        the stacked layers' gradients (swarm_ppo_ensemble_epoch_grad and its
+        deep twin)."""
         self.optimizer.zero_grad(set_to_none=True)
         off = 0
         for t in layers:
@@ -317,12 +456,14 @@ class EnsembleTorchModel:
 
     def _member_optimizer_state(self, m: int):
         """Member m's Adam state in the form a stock TorchModel's optimizer
-        loads (parameters 0..5 in ActorCriticMLP's order), or None."""
+        loads (parameters in the member module's order, which is that of
+        ppo_layers()), or None."""
         if self.optimizer is None:
             return None
         full = self.optimizer.state_dict()
         state = {}
-        for i, p in enumerate(self.model.ppo_layers()):
+        layers = self.model.ppo_layers()
+        for i, p in enumerate(layers):
             st = self.optimizer.state.get(p)
             if not st:
                 continue
@@ -331,13 +472,15 @@ class EnsembleTorchModel:
                 if isinstance(v, torch.Tensor):
                     v = (v[m] if v.shape == p.shape else v).detach().clone()
                 state[i][key] = v
-        groups = [{**{k: v for k, v in g.items() if k != "params"}, "params": list(range(6))}
+        groups = [{**{k: v for k, v in g.items() if k != "params"},
+                   "params": list(range(len(layers)))}
                   for g in full["param_groups"][:1]]
         return {"state": state, "param_groups": groups}
 
     def export_member(self, m: int, filename: str = "model", directory: str = "Models"):
         """Write member m alone, in the file format of TorchModel.export_model:
-        a stock TorchModel(ActorCriticMLP(...)) restores it with
+        a stock TorchModel(ActorCriticMLP(...)) -- for a deep ensemble
+        TorchModel(DeepActorCriticMLP(...)) -- restores it with
         restore_model_state, so a trained member can be deployed alone."""
         if not 0 <= m < self.n_members:
             raise IndexError(f"member {m} of {self.n_members}")
@@ -363,3 +506,26 @@ class EnsembleTorchModel:
                 for v in st.values():
                     if isinstance(v, torch.Tensor) and v.shape == p.shape:
                         v[dst].copy_(v[src])
+
+    @torch.no_grad()
+    def select_members(self, parent_of, with_optimizer_state: bool = True):
+        """Member i becomes a copy of member parent_of[i] (weights and, with
+        with_optimizer_state, Adam moments): one gather over every stacked
+        tensor, so a member that is both a source and a destination is read
+        before it is overwritten -- parent_of = [1, 0, 0] swaps members 0 and
+        1, which sequential copy_member calls do not.  The copies are in
+        place: a captured PPO graph stays valid.  Sampling seeds and call
+        counters stay with the slot."""
+        parent_of = [int(i) for i in parent_of]
+        if len(parent_of) != self.n_members:
+            raise ValueError(f"{len(parent_of)} parents for {self.n_members} members")
+        if any(not 0 <= i < self.n_members for i in parent_of):
+            raise IndexError(f"parents must be members 0..{self.n_members - 1}")
+        for p in self.model.ppo_layers():
+            index = torch.tensor(parent_of, dtype=torch.long, device=p.device)
+            p.copy_(p.index_select(0, index))
+            st = self.optimizer.state.get(p) if self.optimizer is not None else None
+            if with_optimizer_state and st:
+                for v in st.values():
+                    if isinstance(v, torch.Tensor) and v.shape == p.shape:
+                        v.copy_(v.index_select(0, index))

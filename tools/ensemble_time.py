@@ -2,6 +2,7 @@
 user writes without it, M single-model calls on the members' slices.
 
   python tools/ensemble_time.py [--members 1 8 64] [--runs 3] [--window 0.25]
+                                [--hidden 128,128]
 
 The workload is 64 envs x 1024 agents (65536 agents a slice), one feature,
 the stock 1-128-(4+1) network, episodes of T = 20 slices; member m owns
@@ -11,6 +12,11 @@ the stock 1-128-(4+1) network, episodes of T = 20 slices; member m owns
            against M x ops.policy_mlp_sample
   epoch    the gradient of one PPO epoch over the episode:
            ops.ppo_ensemble_epoch_grad against M x ops.ppo_epoch_grad
+
+With --hidden h1,h2[,h3] the network is the deep stack 1-h1-..-hL-(4+1)
+(EnsembleDeepActorCriticMLP): ops.policy_deep_ensemble_sample against M x
+ops.policy_deep_sample, and the deep ops.ppo_ensemble_epoch_grad against M x
+the deep ops.ppo_epoch_grad.
 
 The loop's kernels are the single-model ones, so the loop is the baseline
 and the ensemble path the code under test; both give the same bits (checked
@@ -27,7 +33,8 @@ import torch
 
 sys.path.insert(0, ".")
 from swarmrl_amd.engine import ops  # noqa: E402
-from swarmrl_amd.networks import ActorCriticMLP, EnsembleActorCriticMLP  # noqa: E402
+from swarmrl_amd.networks import (ActorCriticMLP, DeepActorCriticMLP,  # noqa: E402
+                                  EnsembleActorCriticMLP, EnsembleDeepActorCriticMLP)
 
 E, A, D, K, HIDDEN, T = 64, 1024, 1, 4, 128, 20
 HYPER = (0.99, 0.95, 0.2, 0.01)  # gamma, lambda, clip epsilon, entropy coefficient
@@ -50,13 +57,19 @@ def timed(fn, seconds):
         calls = max(calls * 2, int(calls * 1.2 * seconds / max(t, 1e-6)))
 
 
-def problem(M, dev):
+def problem(M, dev, hidden=HIDDEN):
+    """hidden: an int (the stock network) or a tuple of widths (the deep stack)."""
     g = torch.Generator().manual_seed(M)
     torch.manual_seed(M)
-    ens = EnsembleActorCriticMLP.from_members(
-        [ActorCriticMLP(D, K, HIDDEN) for _ in range(M)]).to(dev)
+    deep = not isinstance(hidden, int)
+    if deep:
+        ens = EnsembleDeepActorCriticMLP.from_members(
+            [DeepActorCriticMLP(D, K, hidden) for _ in range(M)]).to(dev)
+    else:
+        ens = EnsembleActorCriticMLP.from_members(
+            [ActorCriticMLP(D, K, hidden) for _ in range(M)]).to(dev)
     n_per = E * A // M
-    p = {"M": M, "n_per": n_per, "ens": ens,
+    p = {"M": M, "n_per": n_per, "ens": ens, "deep": deep,
          "obs": torch.randn(M, n_per, D, generator=g).to(dev),
          "seeds": torch.randint(0, 2 ** 62, (M,), generator=g).to(dev),
          "ftab": torch.tensor([0.0, 10.0, 0.0, 0.0], device=dev),
@@ -78,6 +91,9 @@ def problem(M, dev):
 
 
 def policy_ensemble(p):
+    if p["deep"]:
+        return ops.policy_deep_ensemble_sample(p["obs"], *p["ens"].rollout_layers(), p["seeds"],
+                                               p["state_e"], 0.0, p["ftab"], p["ttab"])
     return ops.policy_ensemble_sample(p["obs"], *p["ens"].rollout_layers(), p["seeds"],
                                       p["state_e"], 0.0, p["ftab"], p["ttab"])
 
@@ -85,6 +101,13 @@ def policy_ensemble(p):
 def policy_loop(p):
     out = []
     for m in range(p["M"]):
+        if p["deep"]:
+            layers = p["members"][m]
+            out.append(ops.policy_deep_sample(p["obs"][m], list(layers[0:-4:2]),
+                                              list(layers[1:-4:2]), layers[-4], layers[-3],
+                                              p["seed_l"][m], p["state_l"][m], 0.0, p["ftab"],
+                                              p["ttab"]))
+            continue
         w1, b1, wa, ba, _, _ = p["members"][m]
         out.append(ops.policy_mlp_sample(p["obs"][m], w1, b1, wa, ba, p["seed_l"][m],
                                          p["state_l"][m], 0.0, p["ftab"], p["ttab"]))
@@ -126,15 +149,19 @@ def main():
     ap.add_argument("--members", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--runs", type=int, default=3, help="alternating runs per figure")
     ap.add_argument("--window", type=float, default=0.25, help="seconds per timed window")
+    ap.add_argument("--hidden", type=str, default=None,
+                    help="h1,h2[,h3]: the deep stack instead of the stock 1-128-(4+1) network")
     args = ap.parse_args()
+    hidden = tuple(int(h) for h in args.hidden.split(",")) if args.hidden else HIDDEN
+    net = "-".join(str(h) for h in ((hidden,) if isinstance(hidden, int) else hidden))
     if not torch.cuda.is_available():
         raise SystemExit("ensemble_time needs a GPU: a CPU run gives no timing")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    print(f"ensemble_time: {E} envs x {A} agents, d_in {D}, 1-{HIDDEN}-({K}+1), T = {T}; "
+    print(f"ensemble_time: {E} envs x {A} agents, d_in {D}, 1-{net}-({K}+1), T = {T}; "
           f"us per call, {args.runs} alternating runs of {args.window} s windows", flush=True)
     for M in args.members:
-        p = problem(M, dev)
+        p = problem(M, dev, hidden)
         check_same_bits(p)
         for name, ens, loop in (("policy", policy_ensemble, policy_loop),
                                 ("epoch", epoch_ensemble, epoch_loop)):
