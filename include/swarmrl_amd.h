@@ -208,6 +208,53 @@ int swarm_engine_set_walls(swarm_engine_t *e, const swarm_wall_t *walls,
  * engine was created (ESPResSo raises for those; synchronous). */
 int swarm_engine_wall_violations(swarm_engine_t *e, uint64_t *count);
 
+/* A rigid rod (EspressoMD.add_rod, espresso.py:546-665: a centre particle
+ * and n - 1 VIRTUAL_SITES_RELATIVE beads): particles [first, first + n) of
+ * every env, the centre first, bead k (k = 0 .. n - 2) in signed slot
+ * m_k = (-1)^k (k / 2 + 1) at centre + m_k delta u (u the centre's
+ * director, delta = (length - thickness) / (n - 1)).  The rod's species
+ * carries its radius (thickness / 2) and its frictions (gamma_t =
+ * friction_trans, gamma_r = friction_rot, mass = rinertia = 0).  fixed: the
+ * centre does not translate (fix = [fixed, fixed, True], espresso.py:631); it
+ * still rotates. */
+typedef struct swarm_rod {
+  int32_t first;
+  int32_t n;
+  double delta;
+  int32_t fixed;
+  int32_t reserved;
+} swarm_rod_t;
+
+/* Replaces the part.add / vs_auto_relate_to calls of add_rod
+ * (espresso.py:626-660); call once, before the first run, like
+ * swarm_engine_set_walls.  The beads are placed onto the centre's line.
+ * From then on every sub-step (and the overlap removal, in which the rod
+ * does not move) runs in one workgroup per env that sums the rod's contact
+ * forces and torque, steps the centre and re-places the beads; the engine
+ * runs no cluster windows and declines swarm_engine_prebuild,
+ * swarm_engine_defer_build, swarm_engine_prebuild_noise and
+ * swarm_engine_hint_defer_check.  2-D periodic boxes without walls; n odd,
+ * n <= 255; at most 4096 particles per env; one rod per engine. */
+int swarm_engine_set_rod(swarm_engine_t *e, const swarm_rod_t *rod);
+
+/* RotateRod's reward on the device (rod_rotation.py:87-219 with
+ * compute_torque_partition_on_rod, colloid_utils.py:29-117), all in fp64:
+ *   step = wrapped (centre angle - hist_ang[e]) in degrees, pushed into the
+ *          env's ring [history]; mean over its filled entries (the
+ *          reference's nanmean over a NaN-initialised roll);
+ *   w_i  = |u x sum_b grad(1 / |r_b - r_i|^12)| + 1e-8 over the rod's
+ *          particles b (xy of the unwrapped positions, no minimum image, u
+ *          the rod's director), normalised over the n_agents colloids;
+ *   out[e][a] = scale * mean * w_a / sum w   (partition = 0: scale * mean /
+ *          n_agents).
+ * agent_idx [n_agents] device int32; hist_ang [E] uint32, ring [E][history]
+ * fp64 and count [E] int32 are the task's device state (hist_ang: the
+ * centre's angle at initialisation, count zeroed), updated by the call; out
+ * device fp32 [E][n_agents].  Asynchronous on the engine stream. */
+int swarm_rod_reward(swarm_engine_t *e, const int32_t *agent_idx, int32_t n_agents,
+                     uint32_t *hist_ang, double *ring, int32_t *count, int32_t history,
+                     double scale, int32_t partition, float *out);
+
 /* Steepest-descent overlap removal (espresso.py:1161-1168): n_steps of
  * dp = clamp(gamma * F, -max_disp, max_disp) per free coordinate. */
 int swarm_engine_remove_overlap(swarm_engine_t *e, int32_t n_steps,

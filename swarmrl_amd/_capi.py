@@ -87,6 +87,17 @@ class SwarmWall(ctypes.Structure):
     ]
 
 
+class SwarmRod(ctypes.Structure):
+    """swarm_rod_t: particles [first, first + n) of every env, bead spacing."""
+    _fields_ = [
+        ("first", ctypes.c_int32),
+        ("n", ctypes.c_int32),
+        ("delta", ctypes.c_double),
+        ("fixed", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 class SwarmVisionParams(ctypes.Structure):
     _fields_ = [
         ("vision_range", ctypes.c_float),
@@ -291,6 +302,11 @@ _SIGNATURES = {
     "swarm_engine_download_directors": (ctypes.c_int, [_P, _P]),
     "swarm_engine_set_walls": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
     "swarm_engine_wall_violations": (ctypes.c_int, [_P, _P]),
+    "swarm_engine_set_rod": (ctypes.c_int, [_P, ctypes.POINTER(SwarmRod)]),
+    "swarm_rod_reward": (
+        ctypes.c_int,
+        [_P, _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _P],
+    ),
     "swarm_neighbor_reduce": (
         ctypes.c_int,
         [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_uint32,

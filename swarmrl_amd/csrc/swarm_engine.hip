@@ -37,6 +37,7 @@
 #include "swarm_ppo.cuh"
 #include "swarm_ensemble.cuh"
 #include "swarm_rnd.cuh"
+#include "swarm_rod.cuh"
 
 namespace {
 
@@ -1490,6 +1491,9 @@ struct swarm_engine {
   unsigned long long* d_rstamp = nullptr;
   float* own_f_swim = nullptr;
   float* own_torque_z = nullptr;
+  // swarm_engine_set_rod: every sub-step runs on k_rod_run (swarm_rod.cuh)
+  bool has_rod = false;
+  swarm::RodArgs rod{};
   void* allocs[96] = {};
   int n_allocs = 0;
 };
@@ -1556,6 +1560,7 @@ void set_lds_attributes() {
   static bool done = false;
   if (done) return;
   const void* fns[] = {reinterpret_cast<const void*>(&swarm::k_global),
+                       reinterpret_cast<const void*>(&swarm::k_rod_run),
                        reinterpret_cast<const void*>(&swarm::k_cluster_build<false, false>),
                        reinterpret_cast<const void*>(&swarm::k_cluster_build<false, true>),
                        reinterpret_cast<const void*>(&swarm::k_cluster_build<true, false>),
@@ -1593,9 +1598,27 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }
+  if (e->has_rod) {
+    hipLaunchKernelGGL(swarm::k_rod_run, dim3(e->n_envs), dim3(1024),
+                       swarm::rod_lds_words(e->n, 1 << (e->lxg + e->lyg)) * 4, e->stream,
+                       e->d_derived, e->st, e->rod, n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg,
+                       sd_mode, g, md);
+    HIP_TRY(hipGetLastError());
+    return SWARM_OK;
+  }
   hipLaunchKernelGGL(swarm::k_global, dim3(e->n_envs), dim3(1024),
                      global_lds_bytes(e->lxg, e->lyg, e->n, e->params.n_dims), e->stream, e->d_derived, e->st, e->sc,
                      n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg, sd_mode, g, md);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+// The rod's beads onto the centre's line (swarm_rod.cuh:rod_place).
+int launch_rod_snap(swarm_engine* e) {
+  const int items = e->n_envs * (e->rod.n - 1);
+  if (items <= 0) return SWARM_OK;
+  hipLaunchKernelGGL(swarm::k_rod_snap, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                     e->stream, e->d_derived, e->st, e->rod, e->n_envs);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
@@ -2505,7 +2528,12 @@ int swarm_engine_upload_state(swarm_engine_t* e, const double* pos, const double
     const int rc = swarm_engine_upload_directors(e, d3.data());
     if (rc) return rc;
   }
-  return swarm_engine_upload_raw(e, q.data(), img.data(), ang.data());
+  const int rc = swarm_engine_upload_raw(e, q.data(), img.data(), ang.data());
+  if (rc || !e->has_rod) return rc;
+  // a rod's beads follow from its centre (the raw upload keeps them as given)
+  if (const int src = launch_rod_snap(e)) return src;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
 }
 
 int swarm_engine_download_state(swarm_engine_t* e, double* pos, double* director, double* velocity) {
@@ -3667,6 +3695,7 @@ int swarm_engine_set_walls(swarm_engine_t* e, const swarm_wall_t* walls, int32_t
   if (const int frc = flush_check(e)) return frc;
   if (n_walls < 0 || n_walls > SWARM_MAX_WALLS) return fail(SWARM_ECAPACITY, "0 <= n_walls <= 16");
   if (n_walls > 0 && !walls) return fail(SWARM_EINVAL, "null walls");
+  if (n_walls > 0 && e->has_rod) return fail(SWARM_EINVAL, "walls with a rod are not supported");
   Derived& d = e->derived;
   d.n_walls = n_walls;
   for (int k = 0; k < n_walls; ++k) {
@@ -3705,6 +3734,66 @@ int swarm_engine_wall_violations(swarm_engine_t* e, uint64_t* count) {
   HIP_TRY(hipMemcpyAsync(&v, e->st.wall_viol, sizeof(v), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   *count = v;
+  return SWARM_OK;
+}
+
+int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
+  if (!e || !rod) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (e->has_rod) return fail(SWARM_EINVAL, "the engine already has a rod");
+  if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "Rod can only be added in 2d");
+  if (!e->params.periodic) return fail(SWARM_EINVAL, "a rod needs a periodic box");
+  if (e->derived.n_walls) return fail(SWARM_EINVAL, "a rod with walls is not supported");
+  if (rod->n < 1 || rod->n % 2 != 1) return fail(SWARM_EINVAL, "n_particles must be uneven");
+  if (rod->n > swarm::kRodMaxParticles)
+    return fail(SWARM_ECAPACITY, "a rod has at most 255 particles");
+  if (e->n > swarm::kRodMaxEnv)
+    return fail(SWARM_ECAPACITY, "an engine with a rod has at most 4096 particles per env");
+  if (rod->first < 0 || rod->first + rod->n > e->n)
+    return fail(SWARM_EINVAL, "rod particles out of range");
+  if (!(rod->delta > 0.0) || !std::isfinite(rod->delta))
+    return fail(SWARM_EINVAL, "rod bead spacing must be positive");
+  // every bead within half a box of the centre: its offset is one int32
+  // fixed-point displacement (swarm_rod.cuh:rod_place)
+  const double half = 0.5 * (rod->n - 1) * rod->delta;
+  if (!(half < 0.49 * std::min(e->params.box[0], e->params.box[1])))
+    return fail(SWARM_EINVAL, "the rod must be shorter than the box");
+  const size_t lds = swarm::rod_lds_words(e->n, 1 << (e->lxg + e->lyg)) * 4;
+  if (lds + sizeof(swarm::PairTables) > kMaxLds)
+    return fail(SWARM_ECAPACITY, "env does not fit the LDS of one workgroup");
+  e->rod.first = rod->first;
+  e->rod.n = rod->n;
+  e->rod.delta = (float)rod->delta;
+  e->rod.fixed = rod->fixed ? 1 : 0;
+  e->has_rod = true;
+  // no cluster windows, and none of what prepares or checks them
+  e->cluster_path = false;
+  e->nlist_path = false;
+  e->noise_table = false;
+  e->wide_run = false;
+  e->env_build = false;
+  e->defer_check = false;
+  e->defer_hint = false;
+  e->prebuilt = false;
+  e->prebuilt_noise_steps = 0;
+  e->ride_stage = 0;
+  if (const int rc = launch_rod_snap(e)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+int swarm_rod_reward(swarm_engine_t* e, const int32_t* agent_idx, int32_t n_agents,
+                     uint32_t* hist_ang, double* ring, int32_t* count, int32_t history,
+                     double scale, int32_t partition, float* out) {
+  if (!e || !agent_idx || !hist_ang || !ring || !count || !out)
+    return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (!e->has_rod) return fail(SWARM_ESTATE, "the engine has no rod");
+  if (n_agents < 1 || history < 1) return fail(SWARM_EINVAL, "n_agents and history must be >= 1");
+  hipLaunchKernelGGL(swarm::k_rod_reward, dim3(e->n_envs), dim3(256), 0, e->stream, e->st, e->rod,
+                     e->d_box, agent_idx, n_agents, hist_ang, ring, count, history, scale,
+                     partition, out);
+  HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
 

@@ -10,8 +10,8 @@ library through the C ABI of include/swarmrl_amd.h.  There is no CPU
 fallback: without a HIP device the engine raises.
 
 Scope of this build: 2-D, periodic box, isotropic spheres
-(WCA), Brownian thermostat.  3-D, walls, rods, Gay-Berne, LB and the Langevin
-integrator raise NotImplementedError.
+(WCA), Brownian thermostat, one rigid rod (add_rod).  Gay-Berne, LB and the
+Langevin integrator raise NotImplementedError.
 """
 
 from __future__ import annotations
@@ -274,6 +274,7 @@ class SwarmEngine(Engine):
         self._species_of: typing.List[int] = []
         self._ext_force = None
         self._walls = []  # swarm_wall_t dicts (add_confining_walls / add_walls)
+        self._rod = None  # add_rod: first index, particles, bead spacing, fixed, type
         self._native: _NativeEngine = None
         self._host_cache = None
         self._view = None
@@ -532,6 +533,127 @@ class SwarmEngine(Engine):
             {type_colloid: {"radius": radius_simunits, "aspect_ratio": aspect_ratio}}
         )
 
+    # limits of the rod kernel (swarm_rod.cuh): the env's state lives in the
+    # LDS of one workgroup
+    ROD_MAX_PARTICLES = 255
+    ROD_MAX_ENV_PARTICLES = 4096
+
+    def add_rod(
+        self,
+        rod_center: Quantity = None,
+        rod_length: Quantity = None,
+        rod_thickness: Quantity = None,
+        rod_start_angle: float = None,
+        n_particles: int = None,
+        friction_trans: Quantity = None,
+        friction_rot: Quantity = None,
+        rod_particle_type: int = None,
+        fixed: bool = True,
+    ):
+        """
+        A rigid rod of n_particles point particles that rotate / move as a
+        whole (espresso.py:546-665): the centre first, then n_particles - 1
+        beads, bead k at centre + (-1)^k (k // 2 + 1) delta u, in every env.
+        Returns the handle of the centre particle.  One rod per engine, 2-D
+        periodic boxes without walls.
+        """
+        self._check_already_initialised()
+        if rod_center is None:
+            rod_center = self.params.box_length / 2.0
+        if rod_length is None:
+            rod_length = self.ureg.Quantity(100, "micrometer")
+        if rod_thickness is None:
+            rod_thickness = self.ureg.Quantity(5, "micrometer")
+        if rod_start_angle is None:
+            rod_start_angle = 0
+        if n_particles is None:
+            n_particles = 101
+        if friction_trans is None and not fixed:
+            raise ValueError(
+                "If you want the rod to move, you must provide a friction coefficient"
+            )
+        if friction_rot is None:
+            raise ValueError("You must provide a rotational friction coefficient")
+        if rod_particle_type is None:
+            raise ValueError("You must provide a particle type for the rod")
+        if self.n_dims != 2:
+            raise ValueError("Rod can only be added in 2d")
+        center_pos = np.array(rod_center.m_as("sim_length"), dtype=float)
+        if center_pos[2] != 0:
+            raise ValueError(f"Rod center z-component must be 0. You gave {rod_center}")
+        if n_particles % 2 != 1:
+            raise ValueError(f"n_particles must be uneven. You gave {n_particles}")
+        if self._rod is not None:
+            raise ValueError("the engine already has a rod (one rod per engine)")
+        if n_particles > self.ROD_MAX_PARTICLES:
+            raise ValueError(
+                f"a rod has at most {self.ROD_MAX_PARTICLES} particles. You gave {n_particles}"
+            )
+        if rod_particle_type in self.colloid_radius_register.keys():
+            raise ValueError(
+                f"The chosen type {rod_particle_type} is already taken. "
+                "The rod needs a particle type of its own"
+            )
+        # the centre is never moved by a translational friction when fixed
+        # (the reference's value is unused then)
+        fric_trans = 1.0 if friction_trans is None else float(
+            friction_trans.m_as("sim_force/sim_velocity"))
+        fric_rot = float(friction_rot.m_as("sim_force * sim_length * sim_time"))
+        partcl_radius = rod_thickness.m_as("sim_length") / 2
+        point_span = rod_length.m_as("sim_length") - 2 * partcl_radius
+        if n_particles > 1 and not point_span > 0:
+            raise ValueError("rod_length must exceed rod_thickness")
+        point_dist = point_span / (n_particles - 1) if n_particles > 1 else 1.0
+        if not point_span < 0.98 * min(self._box[0], self._box[1]):
+            raise ValueError("the rod must be shorter than the box")
+        rod = {
+            "first": len(self._types_list), "n": int(n_particles), "delta": float(point_dist),
+            "fixed": bool(fixed), "type": int(rod_particle_type),
+        }
+        self._validate_rod(rod)
+        self._rod = rod
+        if point_dist > 2 * partcl_radius:
+            logger.warning(
+                "your rod has holes. "
+                f"Particle radius {partcl_radius} "
+                f"particle_distance {point_dist} "
+                "(both in simulation units)"
+            )
+        # no mass or rotational inertia: no thermal velocity noise
+        key = (float(partcl_radius), fric_trans, fric_rot, 0.0, 0.0)
+        director = _vector_from_angles(np.pi / 2, rod_start_angle)
+        director[2] = 0.0
+        center_part = self._register_particle(
+            [center_pos] * self.n_envs, [director] * self.n_envs, rod_particle_type, key
+        )
+        for k in range(n_particles - 1):
+            dist_to_center = (-1) ** k * (k // 2 + 1) * point_dist
+            pos_virt = center_pos + dist_to_center * director
+            self._register_particle(
+                [pos_virt] * self.n_envs, [director] * self.n_envs, rod_particle_type, key
+            )
+        self.colloid_radius_register.update(
+            {rod_particle_type: {"radius": partcl_radius, "aspect_ratio": 1.0}}
+        )
+        return center_part
+
+    def _validate_rod(self, rod=None):
+        """What the rod path cannot run: refused when the rod is added and
+        again at the first integrate (walls or colloids added after it)."""
+        rod = self._rod if rod is None else rod
+        if rod is None:
+            return
+        if self._walls:
+            raise NotImplementedError("a rod together with walls is not implemented")
+        if not self.params.periodic:
+            raise NotImplementedError("a rod in a non-periodic box is not implemented")
+        total = max(len(self._types_list), rod["first"] + rod["n"])
+        if total > self.ROD_MAX_ENV_PARTICLES:
+            raise ValueError(
+                f"an engine with a rod holds at most {self.ROD_MAX_ENV_PARTICLES} particles "
+                f"per env. You have {total}"
+            )
+
     def add_const_force_to_colloids(self, force: Quantity, type: int):
         """Constant external force on every colloid of a type (espresso.py:834-851)."""
         f = np.asarray(force.m_as("sim_force"), dtype=float)
@@ -681,6 +803,12 @@ class SwarmEngine(Engine):
                 arr[k].offset = float(w.get("offset", 0.0))
             self._native.call("swarm_engine_set_walls", ctypes.cast(arr, ctypes.c_void_p),
                               len(self._walls))
+
+        if self._rod is not None:
+            rod = _capi.SwarmRod()
+            rod.first, rod.n = self._rod["first"], self._rod["n"]
+            rod.delta, rod.fixed = self._rod["delta"], 1 if self._rod["fixed"] else 0
+            self._native.call("swarm_engine_set_rod", ctypes.byref(rod))
 
         self._types_host = np.asarray(self._types_list, dtype=np.int32)
         self._types_device = torch.as_tensor(self._types_host, device=self.device)
@@ -1023,6 +1151,7 @@ class SwarmEngine(Engine):
         if not self.integration_initialised:
             self.slice_idx = 0
             self.step_idx = 0
+            self._validate_rod()
             self._setup_interactions()
             self._remove_overlap()
             self._init_h5_output()
