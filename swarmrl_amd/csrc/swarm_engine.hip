@@ -3799,176 +3799,9 @@ int swarm_rod_reward(swarm_engine_t* e, const int32_t* agent_idx, int32_t n_agen
 
 }  // extern "C"
 
-int swarm_sample_actions(const float* logits, int32_t n, int32_t k, uint64_t seed,
-                         uint64_t* state, int32_t n_state, float explore_p,
-                         const float* f_table, const float* t_table, int64_t* out_idx,
-                         float* out_logp, float* out_f, float* out_t, void* stream) {
-  if (!logits || !state || !f_table || !t_table || !out_idx || !out_logp || !out_f || !out_t)
-    return fail(SWARM_EINVAL, "null argument");
-  if (k < 1 || k > swarm::kMaxActions) return fail(SWARM_ECAPACITY, "1 <= k <= 64 actions");
-  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
-    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
-  if (n <= 0) return SWARM_OK;
-  if (n_state < (n + 63) / 64) return fail(SWARM_EINVAL, "state needs ceil(n / 64) counters");
-  hipLaunchKernelGGL(swarm::k_sample_actions, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), logits, n, k, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), reinterpret_cast<unsigned long long*>(state),
-                     explore_p, f_table, t_table, out_idx, out_logp, out_f, out_t);
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-
-namespace {
-// The rollout policy launch (swarm_policy_mlp_sample); ride: the engine whose
-// deferred build's last stage (the cluster build) rides along as extra
-// workgroups of the same launch (k_policy_cbuild), or null.
-int policy_launch(const float* obs, int32_t n, int32_t d_in, const float* w1, const float* b1,
-                  int32_t hidden, const float* w2, const float* b2, int32_t k, uint64_t seed,
-                  uint64_t* state, int32_t n_state, float explore_p, const float* f_table,
-                  const float* t_table, int64_t* out_idx, float* out_logp, float* out_f,
-                  float* out_t, float* out_logits, void* stream, swarm_engine* ride) {
-  if (!obs || !w1 || !b1 || !w2 || !b2 || !state || !f_table || !t_table || !out_idx ||
-      !out_logp || !out_f || !out_t)
-    return fail(SWARM_EINVAL, "null argument");
-  if (d_in < 1 || d_in > swarm::kMlpMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 16");
-  if (hidden < 1 || hidden > swarm::kMlpMaxHidden)
-    return fail(SWARM_ECAPACITY, "1 <= hidden <= 256");
-  if (k < 1 || k > swarm::kMlpMaxActions) return fail(SWARM_ECAPACITY, "1 <= k <= 16 actions");
-  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
-    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
-  if (n <= 0) return SWARM_OK;
-  if (n_state < (n + 63) / 64) return fail(SWARM_EINVAL, "state needs ceil(n / 64) counters");
-  // lanes per agent: enough waves to cover the SIMDs when agents are few
-  const int G = n <= 16384 ? 4 : (n <= 65536 ? 2 : 1);
-  const bool small_in = d_in <= 4, small_k = k <= 4;
-  const unsigned blocks = (unsigned)(((long)n * G + 255) / 256);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  auto* st = reinterpret_cast<unsigned long long*>(state);
-  const swarm::MlpArgs m{obs,   n,          d_in,    w1,      b1,       hidden, w2,
-                         b2,    k,          k0,      k1,      st,       explore_p, f_table,
-                         t_table, out_idx,  out_logp, out_f,  out_t,    out_logits};
-  // the build stage may only ride along on the engine's stream: stages 1-2
-  // and the run that consumes the build are ordered on it
-  if (ride && s == ride->stream && ride->ride_stage == 3 && G == 4 && small_in && small_k) {
-    // policy blocks of 1024 threads (256 agents: whole counter groups) and
-    // one cluster-build workgroup per env
-    const int pblocks = (int)(((long)n * G + 1023) / 1024);
-    const size_t plds = (size_t)(hidden * swarm::MlpRow<4, 4>::kStride + 4) * sizeof(float);
-    const size_t lds = std::max(plds, build_lds_bytes(ride->n, ride->sc.pair_cap));
-    hipLaunchKernelGGL((k_policy_cbuild<4, 4, 4>), dim3((unsigned)(pblocks + ride->n_envs)),
-                       dim3(1024), lds, s, m, ride->n_envs, ride->st, ride->sc);
-    HIP_TRY(hipGetLastError());
-    ride->ride_stage = 0;
-    ride->prebuilt = true;
-    return SWARM_OK;
-  }
-  if (ride && ride->ride_stage > 0) {
-    const int rc = flush_ride_along(ride);
-    if (rc) return rc;
-  }
-#define SWARM_MLP(GG, DD, KK)                                                                   \
-  hipLaunchKernelGGL((swarm::k_policy_mlp_sample<GG, DD, KK>), dim3(blocks), dim3(256),        \
-                     (size_t)(hidden * swarm::MlpRow<DD, KK>::kStride + KK) * sizeof(float), s, m)
-#define SWARM_MLP_G(GG)                 \
-  do {                                  \
-    if (small_in && small_k)            \
-      SWARM_MLP(GG, 4, 4);              \
-    else if (small_in)                  \
-      SWARM_MLP(GG, 4, 16);             \
-    else if (small_k)                   \
-      SWARM_MLP(GG, 16, 4);             \
-    else                                \
-      SWARM_MLP(GG, 16, 16);            \
-  } while (0)
-  if (G == 4)
-    SWARM_MLP_G(4);
-  else if (G == 2)
-    SWARM_MLP_G(2);
-  else
-    SWARM_MLP_G(1);
-#undef SWARM_MLP_G
-#undef SWARM_MLP
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-}  // namespace
-
-int swarm_policy_mlp_sample(const float* obs, int32_t n, int32_t d_in, const float* w1,
-                            const float* b1, int32_t hidden, const float* w2, const float* b2,
-                            int32_t k, uint64_t seed, uint64_t* state, int32_t n_state,
-                            float explore_p, const float* f_table, const float* t_table,
-                            int64_t* out_idx, float* out_logp, float* out_f, float* out_t,
-                            float* out_logits, void* stream) {
-  return policy_launch(obs, n, d_in, w1, b1, hidden, w2, b2, k, seed, state, n_state, explore_p,
-                       f_table, t_table, out_idx, out_logp, out_f, out_t, out_logits, stream,
-                       nullptr);
-}
-
-int swarm_engine_policy_mlp_sample(swarm_engine_t* e, const float* obs, int32_t n, int32_t d_in,
-                                   const float* w1, const float* b1, int32_t hidden,
-                                   const float* w2, const float* b2, int32_t k, uint64_t seed,
-                                   uint64_t* state, int32_t n_state, float explore_p,
-                                   const float* f_table, const float* t_table, int64_t* out_idx,
-                                   float* out_logp, float* out_f, float* out_t, float* out_logits,
-                                   void* stream) {
-  if (!e) return fail(SWARM_EINVAL, "null engine");
-  if (const int frc = flush_check(e)) return frc;
-  return policy_launch(obs, n, d_in, w1, b1, hidden, w2, b2, k, seed, state, n_state, explore_p,
-                       f_table, t_table, out_idx, out_logp, out_f, out_t, out_logits, stream, e);
-}
-
-namespace {
-// The limits of the deep kernels (swarm_deep.cuh); null: within them.
-const char* deep_limits(int32_t d_in, int32_t n_hidden, const int32_t* widths, int32_t k) {
-  if (n_hidden < swarm::kDeepMinLayers || n_hidden > swarm::kDeepMaxLayers)
-    return "2 <= n_hidden <= 3 hidden layers";
-  if (d_in < 1 || d_in > swarm::kDeepMaxIn) return "1 <= d_in <= 32";
-  if (k < 1 || k > swarm::kDeepMaxActions) return "1 <= k <= 16 actions";
-  for (int l = 0; l < n_hidden; ++l)
-    if (widths[l] < 1 || widths[l] > swarm::kDeepMaxWidth) return "1 <= hidden width <= 128";
-  return nullptr;
-}
-}  // namespace
-
-int swarm_policy_deep_sample(const float* obs, int32_t n, int32_t d_in, int32_t n_hidden,
-                             const int32_t* widths, const float* const* w, const float* const* b,
-                             const float* wa, const float* ba, int32_t k, uint64_t seed,
-                             uint64_t* state, int32_t n_state, float explore_p,
-                             const float* f_table, const float* t_table, int64_t* out_idx,
-                             float* out_logp, float* out_f, float* out_t, float* out_logits,
-                             void* stream) {
-  if (!obs || !widths || !w || !b || !wa || !ba || !state || !f_table || !t_table || !out_idx ||
-      !out_logp || !out_f || !out_t)
-    return fail(SWARM_EINVAL, "null argument");
-  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
-  swarm::DeepArgs dp{};
-  dp.n_hidden = n_hidden;
-  for (int l = 0; l < n_hidden; ++l) {
-    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
-    dp.width[l] = widths[l];
-    dp.w[l] = w[l];
-    dp.b[l] = b[l];
-  }
-  dp.wa = wa;
-  dp.ba = ba;
-  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
-    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
-  if (n <= 0) return SWARM_OK;
-  if (n_state < (n + 63) / 64) return fail(SWARM_EINVAL, "state needs ceil(n / 64) counters");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const swarm::MlpArgs m{obs,     n,       d_in,     nullptr, nullptr, 0,     nullptr,
-                         nullptr, k,       (uint32_t)seed, (uint32_t)(seed >> 32),
-                         reinterpret_cast<unsigned long long*>(state), explore_p, f_table,
-                         t_table, out_idx, out_logp, out_f,   out_t,   out_logits};
-  const unsigned blocks = (unsigned)((n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
-  if (k <= 4)
-    hipLaunchKernelGGL(swarm::k_policy_deep_sample<4>, dim3(blocks), dim3(256), 0, s, m, dp);
-  else
-    hipLaunchKernelGGL(swarm::k_policy_deep_sample<16>, dim3(blocks), dim3(256), 0, s, m, dp);
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
+// the policy samplers and the PPO epochs (swarm_sample_actions ..
+// swarm_ppo_deep_ensemble_epoch_grad)
+#include "swarm_learn_host.cuh"
 
 int swarm_engine_defer_build(swarm_engine_t* e, int32_t* deferred) {
   if (!e || !deferred) return fail(SWARM_EINVAL, "null argument");
@@ -3982,869 +3815,6 @@ int swarm_engine_defer_build(swarm_engine_t* e, int32_t* deferred) {
   e->ride_stage = 1;
   e->vgrid_ready = false;
   *deferred = 1;
-  return SWARM_OK;
-}
-
-namespace {
-struct PpoWorkspace {
-  size_t values, adv, dv, spart, table, partial, ticket, total;
-};
-PpoWorkspace ppo_workspace(long n, long S, int d, int hidden, int k) {
-  PpoWorkspace w;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  w.values = 0;
-  w.adv = up(w.values + (size_t)n * 4);
-  w.dv = up(w.adv + (size_t)n * 4);
-  w.spart = up(w.dv + (size_t)n * 4);
-  w.table = up(w.spart + (size_t)((S + 255) / 256) * 2 * sizeof(double));
-  // unit rows: at most 256 units x PpoTable<32, 16>::kStride floats
-  w.partial = up(w.table + (size_t)swarm::kPpoMaxHidden * swarm::PpoTable<32, 16>::kStride * 4);
-  w.ticket = up(w.partial + (size_t)swarm::kPpoBlocks * swarm::ppo_grad_size(d, hidden, k) * 4);
-  w.total = up(w.ticket + 4);
-  return w;
-}
-}  // namespace
-
-int64_t swarm_ppo_workspace_bytes(int32_t T, int32_t S, int32_t d_in, int32_t hidden,
-                                  int32_t k) {
-  if (T < 1 || S < 1 || d_in < 1 || hidden < 1 || k < 1) return -1;
-  return (int64_t)ppo_workspace((long)T * S, S, d_in, hidden, k).total;
-}
-
-// swarm_ppo_profile: HIP events around every k_ppo_grads launch of this
-// thread (bench.py's roofline of the update); not under graph capture.
-namespace {
-struct PpoProfile {
-  bool on = false;
-  int reps = 1;  // back-to-back k_ppo_grads launches per epoch while timing
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-};
-thread_local PpoProfile g_ppo_prof;
-}  // namespace
-
-int swarm_ppo_profile(int32_t enable, double* grads_ms, int32_t* launches) {
-  int32_t pairs = 0;
-  const int rc = read_event_pairs(g_ppo_prof.ev, grads_ms, &pairs);
-  if (launches) *launches = pairs * g_ppo_prof.reps;
-  g_ppo_prof.reps = enable > 0 ? enable : 1;
-  g_ppo_prof.on = enable > 0;
-  return rc;
-}
-
-namespace {
-// Workgroups of `fn` resident at once on a whole MI355X (256 CUs).  The grid
-// size sets the fixed cross-block summation order of the gradient, so it is
-// a function of the kernel and n only -- never of the device it runs on or
-// its partition mode: replicas on any GPUs sum in the same order and stay
-// bit-identical.
-constexpr int kPpoOrderCUs = 256;
-int ppo_resident_blocks(const void* fn, int threads, size_t lds) {
-  const int cus = kPpoOrderCUs;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess ||
-      per_cu < 1)
-    per_cu = 1;
-  return std::max(1, per_cu * cus);
-}
-}  // namespace
-
-namespace {
-int ppo_epoch(const float* x, int32_t T, int32_t S, int32_t d_in, const int64_t* actions,
-              const float* old_logp, const float* rewards, const float* w1, const float* b1,
-              int32_t hidden, const float* wa, const float* ba, int32_t k, const float* wc,
-              const float* bc, float gamma, float lambda, float clip_eps, float entropy_coef,
-              void* workspace, int64_t workspace_bytes, float* grad, void* stream,
-              const swarm_adam_t* adam) {
-  if (!x || !actions || !old_logp || !rewards || !w1 || !b1 || !wa || !ba || !wc || !bc ||
-      !workspace || !grad)
-    return fail(SWARM_EINVAL, "null argument");
-  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
-  if ((long)T * S > INT32_MAX) return fail(SWARM_ECAPACITY, "T x S < 2^31 samples");
-  if (d_in < 1 || d_in > swarm::kPpoMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 32");
-  if (hidden < 1 || hidden > swarm::kPpoMaxHidden)
-    return fail(SWARM_ECAPACITY, "1 <= hidden <= 256");
-  if (k < 1 || k > swarm::kPpoMaxK) return fail(SWARM_ECAPACITY, "1 <= k <= 16 actions");
-  const int n = T * S;
-  const PpoWorkspace ws = ppo_workspace(n, S, d_in, hidden, k);
-  if (workspace_bytes < (int64_t)ws.total)
-    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_workspace_bytes");
-  char* base = static_cast<char*>(workspace);
-  float* values = reinterpret_cast<float*>(base + ws.values);
-  float* adv = reinterpret_cast<float*>(base + ws.adv);
-  float* dv = reinterpret_cast<float*>(base + ws.dv);
-  float* partial = reinterpret_cast<float*>(base + ws.partial);
-  float* table = reinterpret_cast<float*>(base + ws.table);
-  double* spart = reinterpret_cast<double*>(base + ws.spart);
-  const int gae_blocks = (S + 255) / 256;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int NW = hidden <= 128 ? 1 : 2;  // waves of 128 units
-  const long tiles = ((long)n + 63) / 64;  // k_ppo_values_split: 64 samples a block
-  // k_ppo_grads: tiles of 128 samples; every block writes its partial row and
-  // the reduce reads exactly the rows written
-  // hidden <= 128: blocks of 4 tile waves (NT), else 2 unit waves (NW);
-  // fewer tiles than 4 per grads block: the 4 waves share each tile (coop)
-  const int NT = NW == 1 ? 4 : 1;
-  const long tiles128 = ((long)n + 127) / 128;
-  const bool coop = NW == 1 && tiles128 < 4L * swarm::kPpoBlocks;
-  int blocks = (int)std::min<long>(coop ? tiles128 : (tiles128 + NT - 1) / NT,
-                                   swarm::kPpoBlocks);
-  const unsigned vblocks = (unsigned)(((n + 3) / 4 + 255) / 256);  // k_ppo_values: 4 a thread
-  // V of every sample, GAE + dL/dV (+ the table), then the gradients
-#define SWARM_PPO(NN, DD, KK)                                                                 \
-  do {                                                                                        \
-    using Tb = swarm::PpoTable<DD, KK>;                                                       \
-    const swarm::PpoPack pk{w1, b1, wa, wc, d_in, hidden, k, 128 * NN, table};                \
-    const int pack_blocks = (128 * NN * Tb::kStride + 255) / 256;                             \
-    const dim3 ggrid((unsigned)(gae_blocks + pack_blocks));                                   \
-    if (n < (1 << 20))                                                                        \
-      hipLaunchKernelGGL((swarm::k_ppo_values_split<DD>), dim3((unsigned)tiles), dim3(256),   \
-                         0, s, x, n, d_in, w1, b1, hidden, wc, bc, values);                   \
-    else                                                                                      \
-      hipLaunchKernelGGL((swarm::k_ppo_values<DD>), dim3(vblocks), dim3(256), 0, s, x, n,     \
-                         d_in, w1, b1, hidden, wc, bc, values);                               \
-    if (T <= 32)                                                                              \
-      hipLaunchKernelGGL((swarm::k_ppo_gae<32, DD, KK>), ggrid, dim3(256), 0, s, rewards,     \
-                         values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, pk);        \
-    else                                                                                      \
-      hipLaunchKernelGGL((swarm::k_ppo_gae<0, DD, KK>), ggrid, dim3(256), 0, s, rewards,      \
-                         values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, pk);        \
-    constexpr int TT = NN == 1 ? 4 : 1;                                                       \
-    if (NN == 1 && coop) SWARM_PPO_GRADS(NN, TT, NN == 1, DD, KK);                            \
-    else SWARM_PPO_GRADS(NN, TT, false, DD, KK);                                              \
-  } while (0)
-#define SWARM_PPO_GRADS(NN, TT, CO, DD, KK)                                                   \
-  do {                                                                                        \
-    const void* fn = reinterpret_cast<const void*>(&swarm::k_ppo_grads<NN, TT, CO, DD, KK>);  \
-    const int lds = swarm::ppo_grads_lds_floats<NN, TT, CO, DD, KK>() * (int)sizeof(float);   \
-    if (lds > 65536)                                                                          \
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-    /* no more blocks than are resident at once: a second round of blocks */                  \
-    /* would leave most SIMDs idle for its tail */                                            \
-    if (!(CO)) blocks = std::min(blocks, ppo_resident_blocks(fn, 64 * NN * TT, lds));         \
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;                                                 \
-    if (g_ppo_prof.on && hipEventCreate(&ev0) == hipSuccess &&                                \
-        hipEventCreate(&ev1) == hipSuccess)                                                   \
-      (void)hipEventRecord(ev0, s);                                                           \
-    for (int rep = 0; rep < (ev1 ? g_ppo_prof.reps : 1); ++rep) /* same partial rows */      \
-      hipLaunchKernelGGL((swarm::k_ppo_grads<NN, TT, CO, DD, KK>), dim3((unsigned)blocks),   \
-                         dim3(64 * NN * TT),                                                  \
-                         (size_t)lds, s, x, n, d_in, w1, b1, hidden, wa, ba, k, wc, bc,       \
-                         actions, old_logp, adv, dv, spart, gae_blocks, table, clip_eps,      \
-                         entropy_coef, partial);                                              \
-    if (ev1) {                                                                                \
-      (void)hipEventRecord(ev1, s);                                                           \
-      g_ppo_prof.ev.emplace_back(ev0, ev1);                                                   \
-    }                                                                                         \
-  } while (0)
-#define SWARM_PPO_H(NN)                          \
-  do {                                           \
-    if (d_in == 1 && k <= 4)                     \
-      SWARM_PPO(NN, 1, 4);                       \
-    else if (d_in <= 4 && k <= 4)                \
-      SWARM_PPO(NN, 4, 4);                       \
-    else if (d_in <= 4)                          \
-      SWARM_PPO(NN, 4, 16);                      \
-    else if (d_in <= 16 && k <= 4)               \
-      SWARM_PPO(NN, 16, 4);                      \
-    else if (d_in <= 16)                         \
-      SWARM_PPO(NN, 16, 16);                     \
-    else if (k <= 4)                             \
-      SWARM_PPO(NN, 32, 4);                      \
-    else                                         \
-      SWARM_PPO(NN, 32, 16);                     \
-  } while (0)
-  if (NW == 1)
-    SWARM_PPO_H(1);
-  else
-    SWARM_PPO_H(2);
-#undef SWARM_PPO_H
-#undef SWARM_PPO_GRADS
-#undef SWARM_PPO
-  const int size = swarm::ppo_grad_size(d_in, hidden, k);
-  if (adam) {  // the optimizer step fused into the reduce
-    swarm::AdamArgs a;
-    a.lr = adam->lr;
-    a.beta1 = adam->beta1;
-    a.beta2 = adam->beta2;
-    a.eps = adam->eps;
-    const int sizes[6] = {hidden * d_in, hidden, k * hidden, k, hidden, 1};
-    a.seg[0] = 0;
-    for (int t = 0; t < 6; ++t) {
-      if (!adam->param[t] || !adam->exp_avg[t] || !adam->exp_avg_sq[t] || !adam->step[t])
-        return fail(SWARM_EINVAL, "null Adam tensor");
-      a.param[t] = adam->param[t];
-      a.m[t] = adam->exp_avg[t];
-      a.v[t] = adam->exp_avg_sq[t];
-      a.step[t] = adam->step[t];
-      a.seg[t + 1] = a.seg[t] + sizes[t];
-    }
-    uint32_t* ticket = reinterpret_cast<uint32_t*>(base + ws.ticket);
-    hipLaunchKernelGGL(swarm::k_ppo_reduce_adam, dim3((unsigned)((size + 63) / 64)), dim3(1024), 0,
-                       s, partial, blocks, size, grad, a, ticket);
-  } else {
-    hipLaunchKernelGGL(swarm::k_ppo_reduce, dim3((unsigned)((size + 63) / 64)), dim3(1024), 0, s,
-                       partial, blocks, size, grad);
-  }
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-}  // namespace
-
-int swarm_ppo_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
-                         const int64_t* actions, const float* old_logp, const float* rewards,
-                         const float* w1, const float* b1, int32_t hidden, const float* wa,
-                         const float* ba, int32_t k, const float* wc, const float* bc,
-                         float gamma, float lambda, float clip_eps, float entropy_coef,
-                         void* workspace, int64_t workspace_bytes, float* grad, void* stream) {
-  return ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, w1, b1, hidden, wa, ba, k, wc, bc,
-                   gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
-                   nullptr);
-}
-
-namespace {
-struct DeepPpoWorkspace {
-  size_t values, adv, dv, spart, partial, total;
-};
-int deep_ppo_grad_size(int d, int n_hidden, const int32_t* widths, int k) {
-  int size = 0, prev = d;
-  for (int l = 0; l < n_hidden; ++l) {
-    size += widths[l] * prev + widths[l];
-    prev = widths[l];
-  }
-  return size + k * prev + k + prev + 1;
-}
-int deep_ppo_blocks(long n) {
-  return (int)std::min<long>((n + swarm::kDeepAgents - 1) / swarm::kDeepAgents,
-                             swarm::kDeepPpoBlocks);
-}
-DeepPpoWorkspace deep_ppo_workspace(long n, long S, int size) {
-  DeepPpoWorkspace w;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  w.values = 0;
-  w.adv = up(w.values + (size_t)n * 4);
-  w.dv = up(w.adv + (size_t)n * 4);
-  w.spart = up(w.dv + (size_t)n * 4);
-  w.partial = up(w.spart + (size_t)((S + 255) / 256) * 2 * sizeof(double));
-  w.total = up(w.partial + (size_t)deep_ppo_blocks(n) * size * 4);
-  return w;
-}
-}  // namespace
-
-int64_t swarm_ppo_deep_workspace_bytes(int32_t T, int32_t S, int32_t d_in, int32_t n_hidden,
-                                       const int32_t* widths, int32_t k) {
-  if (T < 1 || S < 1 || !widths || deep_limits(d_in, n_hidden, widths, k)) return -1;
-  if ((long)T * S > INT32_MAX) return -1;
-  return (int64_t)deep_ppo_workspace((long)T * S, S,
-                                     deep_ppo_grad_size(d_in, n_hidden, widths, k)).total;
-}
-
-int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
-                              const int64_t* actions, const float* old_logp,
-                              const float* rewards, int32_t n_hidden, const int32_t* widths,
-                              const float* const* w, const float* const* b, const float* wa,
-                              const float* ba, int32_t k, const float* wc, const float* bc,
-                              float gamma, float lambda, float clip_eps, float entropy_coef,
-                              void* workspace, int64_t workspace_bytes, float* grad,
-                              void* stream) {
-  if (!x || !actions || !old_logp || !rewards || !widths || !w || !b || !wa || !ba || !wc ||
-      !bc || !workspace || !grad)
-    return fail(SWARM_EINVAL, "null argument");
-  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
-  if ((long)T * S > INT32_MAX) return fail(SWARM_ECAPACITY, "T x S < 2^31 samples");
-  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
-  swarm::DeepPpoArgs p{};
-  p.net.n_hidden = n_hidden;
-  int off = 0, prev = d_in;
-  for (int l = 0; l < n_hidden; ++l) {
-    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
-    p.net.width[l] = widths[l];
-    p.net.w[l] = w[l];
-    p.net.b[l] = b[l];
-    p.off_w[l] = off;
-    off += widths[l] * prev;
-    p.off_b[l] = off;
-    off += widths[l];
-    prev = widths[l];
-  }
-  p.net.wa = wa;
-  p.net.ba = ba;
-  p.off_wa = off;
-  off += k * prev;
-  p.off_ba = off;
-  off += k;
-  p.off_wc = off;
-  off += prev;
-  p.off_bc = off;
-  p.size = off + 1;
-  const int n = T * S;
-  const DeepPpoWorkspace ws = deep_ppo_workspace(n, S, p.size);
-  if (workspace_bytes < (int64_t)ws.total)
-    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_deep_workspace_bytes");
-  char* base = static_cast<char*>(workspace);
-  float* values = reinterpret_cast<float*>(base + ws.values);
-  float* adv = reinterpret_cast<float*>(base + ws.adv);
-  float* dv = reinterpret_cast<float*>(base + ws.dv);
-  double* spart = reinterpret_cast<double*>(base + ws.spart);
-  p.x = x;
-  p.n = n;
-  p.d = d_in;
-  p.k = k;
-  p.wc = wc;
-  p.bc = bc;
-  p.actions = actions;
-  p.old_logp = old_logp;
-  p.adv = adv;
-  p.dvalue = dv;
-  p.gae_part = spart;
-  const int gae_blocks = (S + 255) / 256;
-  p.n_part = gae_blocks;
-  p.clip_eps = clip_eps;
-  p.c_ent = entropy_coef;
-  p.partial = reinterpret_cast<float*>(base + ws.partial);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const unsigned tiles = (unsigned)(((long)n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
-  const int blocks = deep_ppo_blocks(n);
-  hipLaunchKernelGGL(swarm::k_ppo_deep_values<8>, dim3(tiles), dim3(512), 0, s, x, n, d_in, p.net,
-                     wc, bc, values);
-  // k_ppo_gae as it stands, without pack workgroups (n_gae = its grid)
-  const swarm::PpoPack none{};
-  if (T <= 32)
-    hipLaunchKernelGGL((swarm::k_ppo_gae<32, 1, 4>), dim3((unsigned)gae_blocks), dim3(256), 0, s,
-                       rewards, values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, none);
-  else
-    hipLaunchKernelGGL((swarm::k_ppo_gae<0, 1, 4>), dim3((unsigned)gae_blocks), dim3(256), 0, s,
-                       rewards, values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, none);
-  const bool three = n_hidden == 3;
-  const int lds = swarm::deep_grads_lds_floats(three) * (int)sizeof(float);
-  int dev = -1;
-  HIP_TRY(hipGetDevice(&dev));
-#define SWARM_DEEP_GRADS(KK, LL)                                                                \
-  do {                                                                                          \
-    /* more than 64 KB of dynamic LDS: allowed once per device (the first call */               \
-    /* of a size is never under capture: callers size the workspace eagerly) */                 \
-    static bool allowed[64] = {};                                                               \
-    if (dev < 0 || dev >= 64 || !allowed[dev]) {                                                \
-      HIP_TRY(hipFuncSetAttribute(                                                              \
-          reinterpret_cast<const void*>(&swarm::k_ppo_deep_grads<KK, LL>),                      \
-          hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                    \
-      if (dev >= 0 && dev < 64) allowed[dev] = true;                                            \
-    }                                                                                           \
-    hipLaunchKernelGGL((swarm::k_ppo_deep_grads<KK, LL>), dim3((unsigned)blocks), dim3(512),    \
-                       (size_t)lds, s, p);                                                      \
-  } while (0)
-  if (k <= 4 && !three)
-    SWARM_DEEP_GRADS(4, false);
-  else if (k <= 4)
-    SWARM_DEEP_GRADS(4, true);
-  else if (!three)
-    SWARM_DEEP_GRADS(16, false);
-  else
-    SWARM_DEEP_GRADS(16, true);
-#undef SWARM_DEEP_GRADS
-  hipLaunchKernelGGL(swarm::k_ppo_reduce, dim3((unsigned)((p.size + 63) / 64)), dim3(1024), 0, s,
-                     p.partial, blocks, p.size, grad);
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-
-int swarm_ppo_epoch_step(const float* x, int32_t T, int32_t S, int32_t d_in,
-                         const int64_t* actions, const float* old_logp, const float* rewards,
-                         int32_t hidden, int32_t k, float gamma, float lambda, float clip_eps,
-                         float entropy_coef, const swarm_adam_t* adam, void* workspace,
-                         int64_t workspace_bytes, float* grad, void* stream) {
-  if (!adam) return fail(SWARM_EINVAL, "null argument");
-  if (!(adam->beta1 >= 0.0f && adam->beta1 < 1.0f && adam->beta2 >= 0.0f && adam->beta2 < 1.0f))
-    return fail(SWARM_EINVAL, "Adam betas must be in [0, 1)");
-  return ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, adam->param[0], adam->param[1],
-                   hidden, adam->param[2], adam->param[3], k, adam->param[4], adam->param[5],
-                   gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
-                   adam);
-}
-
-// ---- ensembles: M independent actor-critic MLPs per launch (swarm_ensemble.cuh)
-
-int swarm_policy_ensemble_sample(const float* obs, int32_t n_members, int32_t n_per,
-                                 int32_t d_in, const float* w1, const float* b1, int32_t hidden,
-                                 const float* w2, const float* b2, int32_t k,
-                                 const uint64_t* seeds, uint64_t* state, int32_t n_state_per,
-                                 float explore_p, const float* f_table, const float* t_table,
-                                 int64_t* out_idx, float* out_logp, float* out_f, float* out_t,
-                                 float* out_logits, void* stream) {
-  if (!obs || !w1 || !b1 || !w2 || !b2 || !seeds || !state || !f_table || !t_table || !out_idx ||
-      !out_logp || !out_f || !out_t)
-    return fail(SWARM_EINVAL, "null argument");
-  if (n_members < 1 || n_members > swarm::kEnsembleMaxMembers)
-    return fail(SWARM_ECAPACITY, "1 <= n_members <= 1024");
-  if (d_in < 1 || d_in > swarm::kMlpMaxIn) return fail(SWARM_ECAPACITY, "1 <= d_in <= 16");
-  if (hidden < 1 || hidden > swarm::kMlpMaxHidden)
-    return fail(SWARM_ECAPACITY, "1 <= hidden <= 256");
-  if (k < 1 || k > swarm::kMlpMaxActions) return fail(SWARM_ECAPACITY, "1 <= k <= 16 actions");
-  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
-    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
-  if (n_per <= 0) return SWARM_OK;
-  if (n_state_per < (n_per + 63) / 64)
-    return fail(SWARM_EINVAL, "state needs ceil(n_per / 64) counters per member");
-  // lanes per agent from the member's own agent count, as policy_launch does
-  // from n: G fixes the order of the hidden-unit sum, so the logits' bits
-  const int G = n_per <= 16384 ? 4 : (n_per <= 65536 ? 2 : 1);
-  const bool small_in = d_in <= 4, small_k = k <= 4;
-  // whole blocks per member: no block, so no counter group, straddles two
-  const dim3 grid((unsigned)(((long)n_per * G + 255) / 256), (unsigned)n_members);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const swarm::EnsembleMlpArgs e{
-      swarm::MlpArgs{obs, n_per, d_in, w1, b1, hidden, w2, b2, k, 0u, 0u,
-                     reinterpret_cast<unsigned long long*>(state), explore_p, f_table, t_table,
-                     out_idx, out_logp, out_f, out_t, out_logits},
-      reinterpret_cast<const unsigned long long*>(seeds), n_state_per};
-#define SWARM_ENS_MLP(GG, DD, KK)                                                               \
-  hipLaunchKernelGGL((swarm::k_policy_ensemble_sample<GG, DD, KK>), grid, dim3(256),           \
-                     (size_t)(hidden * swarm::MlpRow<DD, KK>::kStride + KK) * sizeof(float), s, e)
-#define SWARM_ENS_MLP_G(GG)             \
-  do {                                  \
-    if (small_in && small_k)            \
-      SWARM_ENS_MLP(GG, 4, 4);          \
-    else if (small_in)                  \
-      SWARM_ENS_MLP(GG, 4, 16);         \
-    else if (small_k)                   \
-      SWARM_ENS_MLP(GG, 16, 4);         \
-    else                                \
-      SWARM_ENS_MLP(GG, 16, 16);        \
-  } while (0)
-  if (G == 4)
-    SWARM_ENS_MLP_G(4);
-  else if (G == 2)
-    SWARM_ENS_MLP_G(2);
-  else
-    SWARM_ENS_MLP_G(1);
-#undef SWARM_ENS_MLP_G
-#undef SWARM_ENS_MLP
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-
-namespace {
-// Every per-member decision of an ensemble epoch, taken from the member's own
-// n = T * S exactly as ppo_epoch takes it from n (the same kernel variants
-// and the same number of grads blocks, the resident-blocks cap of the
-// single-model kernel included): a member sums in the single call's order.
-struct PpoEnsemblePlan {
-  bool coop;
-  int blocks;        // grads blocks (= partial rows) per member
-  int table_floats;  // the member's parameter table
-};
-
-template <int NN, int DD, int KK>
-PpoEnsemblePlan ppo_ensemble_plan(long n) {
-  constexpr int TT = NN == 1 ? 4 : 1;
-  const long tiles128 = (n + 127) / 128;
-  PpoEnsemblePlan pl;
-  pl.coop = NN == 1 && tiles128 < 4L * swarm::kPpoBlocks;
-  pl.blocks = (int)std::min<long>(pl.coop ? tiles128 : (tiles128 + TT - 1) / TT,
-                                  swarm::kPpoBlocks);
-  if (!pl.coop) {
-    const void* fn = reinterpret_cast<const void*>(&swarm::k_ppo_grads<NN, TT, false, DD, KK>);
-    const int lds = swarm::ppo_grads_lds_floats<NN, TT, false, DD, KK>() * (int)sizeof(float);
-    if (lds > 65536)
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    pl.blocks = std::min(pl.blocks, ppo_resident_blocks(fn, 64 * NN * TT, lds));
-  }
-  pl.table_floats = 128 * NN * swarm::PpoTable<DD, KK>::kStride;
-  return pl;
-}
-
-template <int NN, int TT, bool CO, int DD, int KK>
-void ppo_ensemble_grads(const swarm::PpoEnsembleArgs& a, hipStream_t s) {
-  const void* fn =
-      reinterpret_cast<const void*>(&swarm::k_ppo_ensemble_grads<NN, TT, CO, DD, KK>);
-  const int lds = swarm::ppo_grads_lds_floats<NN, TT, CO, DD, KK>() * (int)sizeof(float);
-  if (lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((swarm::k_ppo_ensemble_grads<NN, TT, CO, DD, KK>),
-                     dim3((unsigned)a.blocks, (unsigned)a.members), dim3(64 * NN * TT),
-                     (size_t)lds, s, a);
-}
-
-// The four launches of ppo_epoch with the member index as grid dimension y.
-template <int NN, int DD, int KK>
-void ppo_ensemble_launch(swarm::PpoEnsembleArgs a, bool coop, hipStream_t s) {
-  constexpr int TT = NN == 1 ? 4 : 1;
-  const unsigned M = (unsigned)a.members;
-  const int n = a.n;
-  a.table_rows = 128 * NN;
-  const int pack_blocks = (a.table_floats + 255) / 256;
-  if (n < (1 << 20))
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_values_split<DD>),
-                       dim3((unsigned)(((long)n + 63) / 64), M), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_values<DD>),
-                       dim3((unsigned)(((n + 3) / 4 + 255) / 256), M), dim3(256), 0, s, a);
-  const dim3 ggrid((unsigned)(a.gae_blocks + pack_blocks), M);
-  if (a.T <= 32)
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<32, DD, KK>), ggrid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<0, DD, KK>), ggrid, dim3(256), 0, s, a);
-  if (NN == 1 && coop)
-    ppo_ensemble_grads<NN, TT, NN == 1, DD, KK>(a, s);
-  else
-    ppo_ensemble_grads<NN, TT, false, DD, KK>(a, s);
-  const int size = swarm::ppo_grad_size(a.d, a.hidden, a.k);
-  hipLaunchKernelGGL(swarm::k_ppo_ensemble_reduce, dim3((unsigned)((size + 63) / 64), M),
-                     dim3(1024), 0, s, a);
-}
-
-// The template widths ppo_epoch picks for (hidden, d_in, k).
-#define SWARM_ENS_PPO_H(NN, CALL)                \
-  do {                                           \
-    if (d_in == 1 && k <= 4)                     \
-      CALL(NN, 1, 4);                            \
-    else if (d_in <= 4 && k <= 4)                \
-      CALL(NN, 4, 4);                            \
-    else if (d_in <= 4)                          \
-      CALL(NN, 4, 16);                           \
-    else if (d_in <= 16 && k <= 4)               \
-      CALL(NN, 16, 4);                           \
-    else if (d_in <= 16)                         \
-      CALL(NN, 16, 16);                          \
-    else if (k <= 4)                             \
-      CALL(NN, 32, 4);                           \
-    else                                         \
-      CALL(NN, 32, 16);                          \
-  } while (0)
-#define SWARM_ENS_PPO(CALL)                      \
-  do {                                           \
-    if (hidden <= 128)                           \
-      SWARM_ENS_PPO_H(1, CALL);                  \
-    else                                         \
-      SWARM_ENS_PPO_H(2, CALL);                  \
-  } while (0)
-
-const char* ppo_ensemble_limits(int32_t M, int32_t T, int32_t S, int32_t d_in, int32_t hidden,
-                                int32_t k) {
-  if (M < 1 || M > swarm::kEnsembleMaxMembers) return "1 <= n_members <= 1024";
-  if ((long)T * S > INT32_MAX) return "T x S < 2^31 samples per member";
-  if (d_in < 1 || d_in > swarm::kPpoMaxIn) return "1 <= d_in <= 32";
-  if (hidden < 1 || hidden > swarm::kPpoMaxHidden) return "1 <= hidden <= 256";
-  if (k < 1 || k > swarm::kPpoMaxK) return "1 <= k <= 16 actions";
-  return nullptr;
-}
-
-PpoEnsemblePlan ppo_ensemble_plan_for(long n, int d_in, int hidden, int k) {
-  PpoEnsemblePlan pl{};
-#define SWARM_ENS_PLAN(NN, DD, KK) pl = ppo_ensemble_plan<NN, DD, KK>(n)
-  SWARM_ENS_PPO(SWARM_ENS_PLAN);
-#undef SWARM_ENS_PLAN
-  return pl;
-}
-
-// Member-major slices: values | adv | dv [M][n], GAE partials
-// [M][2 gae_blocks] (fp64), tables [M][table_floats], block partials
-// [M][blocks][size] -- sized by the blocks a member launches.
-struct PpoEnsembleWorkspace {
-  size_t values, adv, dv, spart, table, partial, total;
-};
-PpoEnsembleWorkspace ppo_ensemble_workspace(size_t M, size_t n, size_t S, int size,
-                                            const PpoEnsemblePlan& pl) {
-  PpoEnsembleWorkspace w;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  w.values = 0;
-  w.adv = up(w.values + M * n * 4);
-  w.dv = up(w.adv + M * n * 4);
-  w.spart = up(w.dv + M * n * 4);
-  w.table = up(w.spart + M * ((S + 255) / 256) * 2 * sizeof(double));
-  w.partial = up(w.table + M * (size_t)pl.table_floats * 4);
-  w.total = up(w.partial + M * (size_t)pl.blocks * (size_t)size * 4);
-  return w;
-}
-}  // namespace
-
-int64_t swarm_ppo_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
-                                           int32_t d_in, int32_t hidden, int32_t k) {
-  if (T < 1 || S < 1 || ppo_ensemble_limits(n_members, T, S, d_in, hidden, k)) return -1;
-  const long n = (long)T * S;
-  const PpoEnsemblePlan pl = ppo_ensemble_plan_for(n, d_in, hidden, k);
-  return (int64_t)ppo_ensemble_workspace((size_t)n_members, (size_t)n, (size_t)S,
-                                         swarm::ppo_grad_size(d_in, hidden, k), pl).total;
-}
-
-int swarm_ppo_ensemble_epoch_grad(const float* x, int32_t n_members, int32_t T, int32_t S,
-                                  int32_t d_in, const int64_t* actions, const float* old_logp,
-                                  const float* rewards, const float* w1, const float* b1,
-                                  int32_t hidden, const float* wa, const float* ba, int32_t k,
-                                  const float* wc, const float* bc, float gamma, float lambda,
-                                  float clip_eps, float entropy_coef, void* workspace,
-                                  int64_t workspace_bytes, float* grad, void* stream) {
-  if (!x || !actions || !old_logp || !rewards || !w1 || !b1 || !wa || !ba || !wc || !bc ||
-      !workspace || !grad)
-    return fail(SWARM_EINVAL, "null argument");
-  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
-  if (const char* why = ppo_ensemble_limits(n_members, T, S, d_in, hidden, k))
-    return fail(SWARM_ECAPACITY, why);
-  const int n = T * S;
-  const PpoEnsemblePlan pl = ppo_ensemble_plan_for(n, d_in, hidden, k);
-  const PpoEnsembleWorkspace ws = ppo_ensemble_workspace(
-      (size_t)n_members, (size_t)n, (size_t)S, swarm::ppo_grad_size(d_in, hidden, k), pl);
-  if (workspace_bytes < (int64_t)ws.total)
-    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_ensemble_workspace_bytes");
-  char* base = static_cast<char*>(workspace);
-  swarm::PpoEnsembleArgs a{};
-  a.x = x;
-  a.actions = actions;
-  a.old_logp = old_logp;
-  a.rewards = rewards;
-  a.w1 = w1;
-  a.b1 = b1;
-  a.wa = wa;
-  a.ba = ba;
-  a.wc = wc;
-  a.bc = bc;
-  a.T = T;
-  a.S = S;
-  a.n = n;
-  a.d = d_in;
-  a.hidden = hidden;
-  a.k = k;
-  a.members = n_members;
-  a.gamma = gamma;
-  a.lambda = lambda;
-  a.clip_eps = clip_eps;
-  a.c_ent = entropy_coef;
-  a.values = reinterpret_cast<float*>(base + ws.values);
-  a.adv = reinterpret_cast<float*>(base + ws.adv);
-  a.dv = reinterpret_cast<float*>(base + ws.dv);
-  a.spart = reinterpret_cast<double*>(base + ws.spart);
-  a.table = reinterpret_cast<float*>(base + ws.table);
-  a.partial = reinterpret_cast<float*>(base + ws.partial);
-  a.grad = grad;
-  a.gae_blocks = (S + 255) / 256;
-  a.table_floats = pl.table_floats;
-  a.blocks = pl.blocks;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define SWARM_ENS_LAUNCH(NN, DD, KK) ppo_ensemble_launch<NN, DD, KK>(a, pl.coop, s)
-  SWARM_ENS_PPO(SWARM_ENS_LAUNCH);
-#undef SWARM_ENS_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-#undef SWARM_ENS_PPO
-#undef SWARM_ENS_PPO_H
-
-// ---- ensembles of deep actor-critic MLPs (swarm_ensemble.cuh over swarm_deep.cuh)
-
-int swarm_policy_deep_ensemble_sample(const float* obs, int32_t n_members, int32_t n_per,
-                                      int32_t d_in, int32_t n_hidden, const int32_t* widths,
-                                      const float* const* w, const float* const* b,
-                                      const float* wa, const float* ba, int32_t k,
-                                      const uint64_t* seeds, uint64_t* state,
-                                      int32_t n_state_per, float explore_p, const float* f_table,
-                                      const float* t_table, int64_t* out_idx, float* out_logp,
-                                      float* out_f, float* out_t, float* out_logits,
-                                      void* stream) {
-  if (!obs || !widths || !w || !b || !wa || !ba || !seeds || !state || !f_table || !t_table ||
-      !out_idx || !out_logp || !out_f || !out_t)
-    return fail(SWARM_EINVAL, "null argument");
-  if (n_members < 1 || n_members > swarm::kEnsembleMaxMembers)
-    return fail(SWARM_ECAPACITY, "1 <= n_members <= 1024");
-  if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
-  swarm::DeepEnsembleArgs e{};
-  e.dp.n_hidden = n_hidden;
-  for (int l = 0; l < n_hidden; ++l) {
-    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
-    e.dp.width[l] = widths[l];
-    e.dp.w[l] = w[l];
-    e.dp.b[l] = b[l];
-  }
-  e.dp.wa = wa;
-  e.dp.ba = ba;
-  if (!(explore_p >= 0.0f && explore_p <= 1.0f))
-    return fail(SWARM_EINVAL, "exploration probability must be in [0, 1]");
-  if (n_per <= 0) return SWARM_OK;
-  if (n_state_per < (n_per + 63) / 64)
-    return fail(SWARM_EINVAL, "state needs ceil(n_per / 64) counters per member");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  e.m = swarm::MlpArgs{obs,     n_per,   d_in,    nullptr, nullptr, 0,  nullptr,
-                       nullptr, k,       0u,      0u,
-                       reinterpret_cast<unsigned long long*>(state), explore_p, f_table,
-                       t_table, out_idx, out_logp, out_f,  out_t,   out_logits};
-  e.seeds = reinterpret_cast<const unsigned long long*>(seeds);
-  e.n_state_per = n_state_per;
-  // whole blocks of 64 agents per member: one workgroup, one counter group
-  const dim3 grid((unsigned)((n_per + swarm::kDeepAgents - 1) / swarm::kDeepAgents),
-                  (unsigned)n_members);
-  if (k <= 4)
-    hipLaunchKernelGGL(swarm::k_policy_deep_ensemble_sample<4>, grid, dim3(256), 0, s, e);
-  else
-    hipLaunchKernelGGL(swarm::k_policy_deep_ensemble_sample<16>, grid, dim3(256), 0, s, e);
-  HIP_TRY(hipGetLastError());
-  return SWARM_OK;
-}
-
-namespace {
-const char* deep_ensemble_limits(int32_t M, int32_t T, int32_t S, int32_t d_in, int32_t n_hidden,
-                                 const int32_t* widths, int32_t k) {
-  if (M < 1 || M > swarm::kEnsembleMaxMembers) return "1 <= n_members <= 1024";
-  if ((long)T * S > INT32_MAX) return "T x S < 2^31 samples per member";
-  return deep_limits(d_in, n_hidden, widths, k);
-}
-
-// Member-major slices: values | adv | dv [M][n], GAE partials
-// [M][2 gae_blocks] (fp64), block partials [M][deep_ppo_blocks(n)][size] --
-// sized by the blocks a member launches.
-DeepPpoWorkspace deep_ppo_ensemble_workspace(size_t M, long n, long S, int size) {
-  DeepPpoWorkspace w;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  w.values = 0;
-  w.adv = up(w.values + M * (size_t)n * 4);
-  w.dv = up(w.adv + M * (size_t)n * 4);
-  w.spart = up(w.dv + M * (size_t)n * 4);
-  w.partial = up(w.spart + M * (size_t)((S + 255) / 256) * 2 * sizeof(double));
-  w.total = up(w.partial + M * (size_t)deep_ppo_blocks(n) * (size_t)size * 4);
-  return w;
-}
-}  // namespace
-
-int64_t swarm_ppo_deep_ensemble_workspace_bytes(int32_t n_members, int32_t T, int32_t S,
-                                                int32_t d_in, int32_t n_hidden,
-                                                const int32_t* widths, int32_t k) {
-  if (T < 1 || S < 1 || !widths ||
-      deep_ensemble_limits(n_members, T, S, d_in, n_hidden, widths, k))
-    return -1;
-  return (int64_t)deep_ppo_ensemble_workspace((size_t)n_members, (long)T * S, S,
-                                              deep_ppo_grad_size(d_in, n_hidden, widths, k))
-      .total;
-}
-
-int swarm_ppo_deep_ensemble_epoch_grad(const float* x, int32_t n_members, int32_t T, int32_t S,
-                                       int32_t d_in, const int64_t* actions,
-                                       const float* old_logp, const float* rewards,
-                                       int32_t n_hidden, const int32_t* widths,
-                                       const float* const* w, const float* const* b,
-                                       const float* wa, const float* ba, int32_t k,
-                                       const float* wc, const float* bc, float gamma,
-                                       float lambda, float clip_eps, float entropy_coef,
-                                       void* workspace, int64_t workspace_bytes, float* grad,
-                                       void* stream) {
-  if (!x || !actions || !old_logp || !rewards || !widths || !w || !b || !wa || !ba || !wc ||
-      !bc || !workspace || !grad)
-    return fail(SWARM_EINVAL, "null argument");
-  if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
-  if (const char* why = deep_ensemble_limits(n_members, T, S, d_in, n_hidden, widths, k))
-    return fail(SWARM_ECAPACITY, why);
-  swarm::DeepPpoEnsembleArgs a{};
-  swarm::DeepPpoArgs& p = a.p;
-  p.net.n_hidden = n_hidden;
-  int off = 0, prev = d_in, nseg = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    if (!w[l] || !b[l]) return fail(SWARM_EINVAL, "null parameter");
-    p.net.width[l] = widths[l];
-    p.net.w[l] = w[l];
-    p.net.b[l] = b[l];
-    p.off_w[l] = off;
-    off += widths[l] * prev;
-    p.off_b[l] = off;
-    off += widths[l];
-    a.seg[nseg++] = widths[l] * prev;
-    a.seg[nseg++] = widths[l];
-    prev = widths[l];
-  }
-  p.net.wa = wa;
-  p.net.ba = ba;
-  p.off_wa = off;
-  off += k * prev;
-  p.off_ba = off;
-  off += k;
-  p.off_wc = off;
-  off += prev;
-  p.off_bc = off;
-  p.size = off + 1;
-  a.seg[nseg++] = k * prev;
-  a.seg[nseg++] = k;
-  a.seg[nseg++] = prev;
-  a.seg[nseg++] = 1;
-  const int n = T * S;
-  const size_t M = (size_t)n_members;
-  const DeepPpoWorkspace ws = deep_ppo_ensemble_workspace(M, n, S, p.size);
-  if (workspace_bytes < (int64_t)ws.total)
-    return fail(SWARM_EINVAL, "workspace smaller than swarm_ppo_deep_ensemble_workspace_bytes");
-  char* base = static_cast<char*>(workspace);
-  float* adv = reinterpret_cast<float*>(base + ws.adv);
-  float* dv = reinterpret_cast<float*>(base + ws.dv);
-  double* spart = reinterpret_cast<double*>(base + ws.spart);
-  const int gae_blocks = (S + 255) / 256;
-  // every decision from the member's own n, as swarm_ppo_deep_epoch_grad takes it
-  const unsigned tiles = (unsigned)(((long)n + swarm::kDeepAgents - 1) / swarm::kDeepAgents);
-  const int blocks = deep_ppo_blocks(n);
-  p.x = x;
-  p.n = n;
-  p.d = d_in;
-  p.k = k;
-  p.wc = wc;
-  p.bc = bc;
-  p.actions = actions;
-  p.old_logp = old_logp;
-  p.adv = adv;
-  p.dvalue = dv;
-  p.gae_part = spart;
-  p.n_part = gae_blocks;
-  p.clip_eps = clip_eps;
-  p.c_ent = entropy_coef;
-  p.partial = reinterpret_cast<float*>(base + ws.partial);
-  a.values = reinterpret_cast<float*>(base + ws.values);
-  a.members = n_members;
-  a.blocks = blocks;
-  a.grad = grad;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const unsigned Mu = (unsigned)n_members;
-  hipLaunchKernelGGL(swarm::k_ppo_deep_ensemble_values<8>, dim3(tiles, Mu), dim3(512), 0, s, a);
-  // k_ppo_ensemble_gae without pack workgroups (its grid is the GAE blocks:
-  // no parameter table, so the one-layer weights stay null)
-  swarm::PpoEnsembleArgs g{};
-  g.rewards = rewards;
-  g.T = T;
-  g.S = S;
-  g.n = n;
-  g.members = n_members;
-  g.gamma = gamma;
-  g.lambda = lambda;
-  g.values = a.values;
-  g.adv = adv;
-  g.dv = dv;
-  g.spart = spart;
-  g.gae_blocks = gae_blocks;
-  if (T <= 32)
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<32, 1, 4>), dim3((unsigned)gae_blocks, Mu),
-                       dim3(256), 0, s, g);
-  else
-    hipLaunchKernelGGL((swarm::k_ppo_ensemble_gae<0, 1, 4>), dim3((unsigned)gae_blocks, Mu),
-                       dim3(256), 0, s, g);
-  const bool three = n_hidden == 3;
-  const int lds = swarm::deep_grads_lds_floats(three) * (int)sizeof(float);
-  int dev = -1;
-  HIP_TRY(hipGetDevice(&dev));
-#define SWARM_DEEP_ENS_GRADS(KK, LL)                                                            \
-  do {                                                                                          \
-    /* more than 64 KB of dynamic LDS: allowed once per device (the first call */               \
-    /* of a size is never under capture: callers size the workspace eagerly) */                 \
-    static bool allowed[64] = {};                                                               \
-    if (dev < 0 || dev >= 64 || !allowed[dev]) {                                                \
-      HIP_TRY(hipFuncSetAttribute(                                                              \
-          reinterpret_cast<const void*>(&swarm::k_ppo_deep_ensemble_grads<KK, LL>),             \
-          hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                    \
-      if (dev >= 0 && dev < 64) allowed[dev] = true;                                            \
-    }                                                                                           \
-    hipLaunchKernelGGL((swarm::k_ppo_deep_ensemble_grads<KK, LL>),                              \
-                       dim3((unsigned)blocks, Mu), dim3(512), (size_t)lds, s, a);               \
-  } while (0)
-  if (k <= 4 && !three)
-    SWARM_DEEP_ENS_GRADS(4, false);
-  else if (k <= 4)
-    SWARM_DEEP_ENS_GRADS(4, true);
-  else if (!three)
-    SWARM_DEEP_ENS_GRADS(16, false);
-  else
-    SWARM_DEEP_ENS_GRADS(16, true);
-#undef SWARM_DEEP_ENS_GRADS
-  hipLaunchKernelGGL(swarm::k_ppo_deep_ensemble_reduce,
-                     dim3((unsigned)((p.size + 63) / 64), Mu), dim3(1024), 0, s, a);
-  HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
 

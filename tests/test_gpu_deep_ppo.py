@@ -23,6 +23,10 @@ CASES = [(2, 1, 2, 4, (16, 16)),
          (5, 517, 32, 16, (128, 128, 128)),
          (40, 150, 2, 4, (128, 128)),       # T > 32: the GAE kernel's uncached loop
          (3, 200, 3, 4, (12, 12, 12))]
+# The (K, L3) template cell of the host's variant ladder that CASES lacks:
+# the 16-action kernel with two hidden layers (CASES has K = 4 with two and
+# with three layers and K = 16 with three); 210 samples, ragged widths.
+LADDER_CASES = [(3, 70, 4, 6, (40, 24))]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -87,7 +91,7 @@ def _fused_grads(loss, net, x, actions, old, rewards):
     return out, flat
 
 
-@pytest.mark.parametrize("T,S,d,k,hidden", CASES)
+@pytest.mark.parametrize("T,S,d,k,hidden", CASES + LADDER_CASES)
 def test_deep_epoch_grad_matches_autograd(T, S, d, k, hidden):
     from swarmrl_amd.losses.proximal_policy_loss import ProximalPolicyLoss
 

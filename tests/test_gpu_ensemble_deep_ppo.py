@@ -85,6 +85,8 @@ def _split(flat, layers):
     (2, 40, 50, 2, 4, (128, 128)),           # T > 32: the GAE kernel's uncached loop
     (2, 5, 517, 32, 16, (128, 128, 128)),    # the limits, K = 16, three layers
     (2, 20, 900, 3, 4, (128, 128)),          # 282 tiles over 256 blocks: several tiles per block
+    (2, 3, 70, 3, 3, (20, 12, 16)),          # the K = 4 kernel with three layers
+    (2, 3, 70, 4, 6, (40, 24)),              # the K = 16 kernel with two layers
 ])
 def test_ensemble_grad_equals_member_calls(M, T, S, d, k, hidden):
     from swarmrl_amd.engine import ops

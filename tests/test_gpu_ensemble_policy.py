@@ -60,12 +60,19 @@ def _loop(p, explore_p, state):
     return tuple(torch.cat([o[i] for o in outs]) for i in range(5))
 
 
+# tests/test_gpu_policy.py::LADDER_CELLS for two members: every (D, K)
+# template arm of the host's variant ladder at 4, 2 and 1 lanes per agent.
+LADDER_CELLS = [(2, n_per, d_in, 100, k, 0.0) for n_per in (1000, 20_000, 70_000)
+                for d_in, k in ((3, 4), (4, 6), (9, 4), (16, 16))]
+
+
 @pytest.mark.parametrize("M,n_per,d_in,hidden,k,explore_p", [
     (3, 70, 3, 128, 4, 0.0),     # a partial counter group; a member boundary inside a block
     (2, 1, 1, 100, 3, 0.0),      # ragged hidden, one agent
     (3, 130, 16, 256, 16, 0.3),  # the wide template, with exploration
     (2, 16385, 3, 128, 4, 0.0),  # G = 2
     (2, 65537, 3, 128, 4, 0.0),  # G = 1
+    *LADDER_CELLS,
 ])
 def test_ensemble_equals_member_calls(M, n_per, d_in, hidden, k, explore_p):
     p = _problem(M, n_per, d_in, hidden, k, seed=n_per)

@@ -66,12 +66,19 @@ def _split(flat, layers):
     return out
 
 
+# tests/test_gpu_ppo.py::LADDER_CELLS for two members: every (D, K) template
+# arm of the host's variant ladder with one and with two unit waves.
+LADDER_DK = [(1, 3), (3, 4), (4, 6), (10, 4), (16, 16), (20, 2), (32, 16)]
+LADDER_CELLS = [(2, 3, 70, d, k, hidden) for hidden in (100, 160) for d, k in LADDER_DK]
+
+
 @pytest.mark.parametrize("M,T,S,d,k,hidden", [
     (3, 5, 37, 3, 4, 128),      # coop: the waves of a block share each tile
     (2, 40, 50, 2, 4, 128),     # T > 32: the GAE kernel's uncached loop
     (2, 7, 333, 10, 3, 100),    # ragged hidden
     (2, 5, 129, 32, 6, 256),    # two unit waves
     (2, 20, 53000, 4, 4, 128),  # >= 2^20 samples a member: packed values, non-coop grads
+    *LADDER_CELLS,
 ])
 def test_ensemble_grad_equals_member_calls(M, T, S, d, k, hidden):
     from swarmrl_amd.engine import ops

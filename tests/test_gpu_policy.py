@@ -107,9 +107,15 @@ def test_agent_uses_fused_path_under_graph_capture(tmp_path):
     assert torch.allclose(out["r"][1], ref, atol=1e-5)
 
 
+# One (d_in, k) per (D, K) template arm of the host's variant ladder, crossed
+# with agent counts of 4, 2 and 1 lanes per agent; hidden 100 is ragged.
+LADDER_CELLS = [(n, d_in, 100, k) for n in (1000, 20_000, 70_000)
+                for d_in, k in ((3, 4), (4, 6), (9, 4), (16, 16))]
+
+
 @pytest.mark.parametrize("n,d_in,hidden,k", [(4096, 3, 128, 4), (1000, 9, 64, 6),
                                              (40_000, 3, 128, 4), (100_000, 16, 256, 16),
-                                             (100_001, 3, 128, 4)])
+                                             (100_001, 3, 128, 4), *LADDER_CELLS])
 def test_fused_mlp_policy_matches_torch_and_sampler(n, d_in, hidden, k):
     """swarm_policy_mlp_sample: logits within fp32 tolerance of the torch
     module (rtol 1e-5, atol 1e-5: summation order differs from the GEMM), and

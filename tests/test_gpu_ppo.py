@@ -81,6 +81,13 @@ def _check(got, want):
         assert (a - b).abs().max().item() <= 2e-3 * b.abs().max().item() + 1e-6, name
 
 
+# One (d, k) per (D, K) template arm of the host's variant ladder; crossed with
+# hidden 100 (one unit wave, ragged) and 160 (two unit waves, ragged) at
+# T = 3, S = 70: 210 samples, two 128-sample tiles with a ragged tail.
+LADDER_DK = [(1, 3), (3, 4), (4, 6), (10, 4), (16, 16), (20, 2), (32, 16)]
+LADDER_CELLS = [(3, 70, d, k, hidden) for hidden in (100, 160) for d, k in LADDER_DK]
+
+
 @pytest.mark.parametrize("T,S,d,k,hidden", [
     (20, 1000, 1, 4, 128),     # concentration-field agents, stock network
     (20, 4096, 4, 4, 128),
@@ -89,6 +96,7 @@ def _check(got, want):
     (3, 64, 2, 4, 64),
     (40, 150, 2, 4, 128),      # T > 32: the GAE kernel's uncached loop
     (20, 53000, 4, 4, 128),    # >= 2^20 samples: the packed two-sample values kernel
+    *LADDER_CELLS,
 ])
 def test_fused_epoch_grad_matches_autograd(T, S, d, k, hidden):
     from swarmrl_amd.losses.proximal_policy_loss import ProximalPolicyLoss
