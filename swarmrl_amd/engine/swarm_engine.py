@@ -272,7 +272,7 @@ class SwarmEngine(Engine):
         self._types_list: typing.List[int] = []
         self._species_keys: typing.List[tuple] = []
         self._species_of: typing.List[int] = []
-        self._ext_force = None
+        self._ext_force = {}  # type -> constant force, simulation units (composed at upload)
         self._walls = []  # swarm_wall_t dicts (add_confining_walls / add_walls)
         self._rod = None  # add_rod: first index, particles, bead spacing, fixed, type
         self._native: _NativeEngine = None
@@ -637,7 +637,7 @@ class SwarmEngine(Engine):
         )
         return center_part
 
-    def _validate_rod(self, rod=None):
+    def _validate_rod(self, rod=None, force_types=None):
         """What the rod path cannot run: refused when the rod is added and
         again at the first integrate (walls or colloids added after it)."""
         rod = self._rod if rod is None else rod
@@ -647,6 +647,10 @@ class SwarmEngine(Engine):
             raise NotImplementedError("a rod together with walls is not implemented")
         if not self.params.periodic:
             raise NotImplementedError("a rod in a non-periodic box is not implemented")
+        # the rod kernel moves the rod from the colloids' contact forces alone
+        force_types = self._ext_force.keys() if force_types is None else force_types
+        if rod["type"] in force_types:
+            raise NotImplementedError("a constant force on the rod's type is not implemented")
         total = max(len(self._types_list), rod["first"] + rod["n"])
         if total > self.ROD_MAX_ENV_PARTICLES:
             raise ValueError(
@@ -655,16 +659,34 @@ class SwarmEngine(Engine):
             )
 
     def add_const_force_to_colloids(self, force: Quantity, type: int):
-        """Constant external force on every colloid of a type (espresso.py:834-851)."""
-        f = np.asarray(force.m_as("sim_force"), dtype=float)
-        if self._ext_force is None:
-            self._ext_force = np.zeros((self.n_envs, len(self._types_list), 3))
-        mask = np.asarray(self._types_list) == type
-        self._ext_force[:, mask, :] = f
+        """Constant external force on every colloid of a type (espresso.py:834-851).
+        The force is kept per type and laid out per colloid when it is handed
+        to the device, so colloids of the type added later (before the first
+        integrate) feel it too.  Not for the rod's type (see _validate_rod)."""
+        f = np.asarray(force.m_as("sim_force"), dtype=float).reshape(3)
+        if int(type) not in self._types_list:
+            raise ValueError(
+                f"Particles of type {type} not added to engine. "
+                f"You currently have {self.colloid_radius_register.keys()}"
+            )
+        self._validate_rod(force_types={*self._ext_force, int(type)})
+        self._ext_force[int(type)] = f
         if self._native is not None:
             self._native.bind_stream()
-            ext = np.ascontiguousarray(self._ext_force.reshape(-1, 3))
-            self._native.call("swarm_engine_set_external_force", ext.ctypes.data)
+            self._upload_ext_force()
+
+    def _compose_ext_force(self):
+        """The forces kept per type as (n_envs, n_particles, 3), from the
+        colloids the engine has now (the same in every env)."""
+        ext = np.zeros((self.n_envs, len(self._types_list), 3))
+        types = np.asarray(self._types_list, dtype=np.int64)
+        for p_type, f in self._ext_force.items():
+            ext[:, types == p_type, :] = f
+        return ext
+
+    def _upload_ext_force(self):
+        ext = np.ascontiguousarray(self._compose_ext_force().reshape(-1, 3))
+        self._native.call("swarm_engine_set_external_force", ext.ctypes.data)
 
     def add_confining_walls(self, wall_type: int):
         """WCA walls on the box faces (espresso.py:667-704): x = 0, x = L_x,
@@ -789,9 +811,8 @@ class SwarmEngine(Engine):
         pos = np.ascontiguousarray(np.stack([np.stack(v) for v in self._pos]), dtype=float)
         dirs = np.ascontiguousarray(np.stack([np.stack(v) for v in self._dir]), dtype=float)
         self._native.call("swarm_engine_upload_state", pos.ctypes.data, dirs.ctypes.data)
-        if self._ext_force is not None:
-            ext = np.ascontiguousarray(self._ext_force.reshape(-1, 3))
-            self._native.call("swarm_engine_set_external_force", ext.ctypes.data)
+        if self._ext_force:
+            self._upload_ext_force()
         if self._walls:
             arr = (_capi.SwarmWall * len(self._walls))()
             for k, w in enumerate(self._walls):

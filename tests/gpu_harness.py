@@ -66,6 +66,21 @@ class Harness:
         self.native.bind_stream()
         self.native.call("swarm_engine_set_torque_xy", t.ctypes.data, 0)
 
+    def set_external_force(self, f_ext):
+        """f_ext: [E][N][3] float64 (the host API's layout; the engine casts it
+        to its [3][E*N] fp32 array)."""
+        f = np.ascontiguousarray(f_ext, np.float64)
+        assert f.shape == (self.E, self.n, 3), f.shape
+        self.native.bind_stream()
+        self.native.call("swarm_engine_set_external_force", f.ctypes.data)
+
+    def window_stats(self):
+        """Per env: the last window's fallback code and cluster-run waves."""
+        fb = np.zeros(self.E, np.int32)
+        w = np.zeros(self.E, np.int32)
+        self.native.call("swarm_engine_window_stats", fb.ctypes.data, w.ctypes.data)
+        return fb, w
+
     def set_walls(self, walls):
         arr = (_capi.SwarmWall * max(1, len(walls)))()
         for k, w in enumerate(walls):

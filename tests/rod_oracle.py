@@ -152,13 +152,15 @@ class ReuseForces:
         return st, info
 
 
-def sd_run(params, state, species, n_steps, rod, gamma=0.1, max_disp=0.1):
+def sd_run(params, state, species, n_steps, rod, gamma=0.1, max_disp=0.1, f_ext=None):
     st = oracle._copy_state(state)
     n = st["ang"].shape[0]
     sp = np.ascontiguousarray(species, dtype=np.uint8)
     fs = np.zeros(n, np.float32)
     tz = np.zeros(n, np.float32)
+    fe = None if f_ext is None else np.ascontiguousarray(f_ext, dtype=np.float32)
     steps = lib().or_rod_sd_run(ctypes.byref(params), n, _ptr(st["q"]), _ptr(st["img"]),
-                                _ptr(st["ang"]), _ptr(sp), _ptr(fs), _ptr(tz), None, int(n_steps),
+                                _ptr(st["ang"]), _ptr(sp), _ptr(fs), _ptr(tz), _ptr(fe),
+                                int(n_steps),
                                 float(gamma), float(max_disp), ctypes.byref(rod))
     return st, steps

@@ -49,6 +49,10 @@ class FakeNative:
         if name == "swarm_engine_set_actions":
             f = np.ctypeslib.as_array(ctypes.cast(args[0], ctypes.POINTER(ctypes.c_float)), (M,))
             self.last_f = f.copy()
+        if name == "swarm_engine_set_external_force":
+            # the C side reads 3 M doubles through the pointer, whatever the caller allocated
+            self.ext = np.ctypeslib.as_array(ctypes.cast(args[0], ctypes.POINTER(ctypes.c_double)),
+                                             (M * 3,)).copy().reshape(self.n_envs, self.n, 3)
 
     def runs(self):
         return [a[0] for n, a in self.calls if n == "swarm_engine_integrate"]
@@ -119,6 +123,144 @@ def test_const_force_actions_marshalled(fake_backend, tmp_path):
     eng = _engine(tmp_path, 5, 9)
     eng.integrate(1, ForceFunction(agents={"0": dummy_models.ConstForce(2.5)}))
     assert np.all(fake_backend.instances[0].last_f == np.float32(2.5))
+
+
+# ------------------- add_const_force_to_colloids (espresso.py:834-851, ext_force)
+SIM_FORCE = refsem.SIM_ENERGY / 1e-6  # newton per simulation force unit
+F_A = np.array([1.0e-13, -2.5e-13, 0.7e-13])  # newton
+F_B = np.array([-3.1e-14, 4.0e-14, 9.9e-14])
+
+
+@pytest.fixture
+def composed(monkeypatch):
+    """Every array SwarmEngine composes for swarm_engine_set_external_force
+    is checked to be (n_envs, n_particles, 3), and to have the rows the
+    backend will read, before the backend gets its pointer."""
+    shapes = []
+    orig = SwarmEngine._compose_ext_force
+
+    def checked(self):
+        ext = orig(self)
+        assert ext.shape == (self.n_envs, len(self._types_list), 3)
+        assert ext.dtype == np.float64
+        if self._native is not None:
+            assert ext.shape[:2] == (self._native.n_envs, self._native.n)
+        shapes.append(ext.shape)
+        return ext
+
+    monkeypatch.setattr(SwarmEngine, "_compose_ext_force", checked)
+    return shapes
+
+
+def _add(eng, n, p_type):
+    ureg = eng.ureg
+    eng.add_colloids(n, ureg.Quantity(0.2, "micrometer"),
+                     ureg.Quantity(np.array([5, 5, 0]), "micrometer"),
+                     ureg.Quantity(1, "micrometer"), type_colloid=p_type)
+
+
+def _two_type_engine(tmp_path, n_envs=2):
+    eng = _engine(tmp_path, 5, 9, n_envs=n_envs)  # one colloid of type 0
+    _add(eng, 2, 1)
+    _add(eng, 1, 0)
+    assert eng._types_list == [0, 1, 1, 0]
+    return eng
+
+
+def _force(eng, newton):
+    return eng.ureg.Quantity(newton, "newton")
+
+
+def _start(eng):
+    eng.integrate(1)  # (the list path of a force function is single-env)
+
+
+def _expect_ext(eng, by_type):
+    types = np.asarray(eng._types_list)
+    want = np.zeros((eng.n_envs, len(types), 3))
+    for t, newton in by_type.items():
+        want[:, types == t, :] = newton / SIM_FORCE
+    return want
+
+
+def test_ext_force_set_before_the_native_engine_exists(fake_backend, composed, tmp_path):
+    """The force reaches the backend as [E * N][3] doubles in simulation
+    units, on the colloids of the type only, the same in every env, and
+    before the overlap removal (which sees it, as the reference's does)."""
+    eng = _two_type_engine(tmp_path)
+    eng.add_const_force_to_colloids(_force(eng, F_A), 1)
+    assert not fake_backend.instances and composed == []  # nothing uploaded yet
+    _start(eng)
+    fake = fake_backend.instances[0]
+    assert composed == [(2, 4, 3)]
+    np.testing.assert_allclose(fake.ext, _expect_ext(eng, {1: F_A}), rtol=1e-6, atol=0)
+    assert np.array_equal(fake.ext[0], fake.ext[1])
+    assert np.all(fake.ext[:, [0, 3]] == 0.0) and np.all(fake.ext[:, [1, 2]] != 0.0)
+    assert np.array_equal(fake.ext[0, 1], fake.ext[0, 2])
+    names = [c[0] for c in fake.calls]
+    assert names.count("swarm_engine_set_external_force") == 1
+    assert names.index("swarm_engine_upload_state") < names.index(
+        "swarm_engine_set_external_force") < names.index("swarm_engine_remove_overlap")
+
+
+def test_ext_force_set_after_the_native_engine_exists(fake_backend, composed, tmp_path):
+    eng = _two_type_engine(tmp_path)
+    _start(eng)
+    fake = fake_backend.instances[0]
+    assert "swarm_engine_set_external_force" not in [c[0] for c in fake.calls]
+    eng.add_const_force_to_colloids(_force(eng, F_A), 0)
+    assert composed == [(2, 4, 3)]
+    np.testing.assert_allclose(fake.ext, _expect_ext(eng, {0: F_A}), rtol=1e-6, atol=0)
+    assert np.all(fake.ext[:, [1, 2]] == 0.0)
+
+
+def test_ext_force_two_types_in_two_calls(fake_backend, composed, tmp_path):
+    """One type before the native engine exists and one after it: both
+    forces are in the second upload; a repeated call replaces its type's."""
+    eng = _two_type_engine(tmp_path, n_envs=3)
+    eng.add_const_force_to_colloids(_force(eng, F_A), 0)
+    _start(eng)
+    fake = fake_backend.instances[0]
+    eng.add_const_force_to_colloids(_force(eng, F_B), 1)
+    np.testing.assert_allclose(fake.ext, _expect_ext(eng, {0: F_A, 1: F_B}), rtol=1e-6, atol=0)
+    assert fake.ext.shape == (3, 4, 3) and np.all(fake.ext != 0.0)
+    eng.add_const_force_to_colloids(_force(eng, F_B), 0)
+    np.testing.assert_allclose(fake.ext, _expect_ext(eng, {0: F_B, 1: F_B}), rtol=1e-6, atol=0)
+    assert composed == 3 * [(3, 4, 3)]
+
+
+def test_ext_force_survives_colloids_added_after_the_call(fake_backend, composed, tmp_path):
+    """Colloids may be added between add_const_force_to_colloids and the
+    first integrate.  The array handed to the backend has a row for every
+    colloid the engine has then (it used to keep the size of the first call,
+    so the backend read past it), a second call with more colloids works,
+    and the force is on every colloid of the type."""
+    eng = _two_type_engine(tmp_path)
+    eng.add_const_force_to_colloids(_force(eng, F_A), 1)
+    _add(eng, 3, 1)
+    _add(eng, 2, 0)
+    eng.add_const_force_to_colloids(_force(eng, F_B), 0)  # (IndexError from a stale mask)
+    _add(eng, 1, 2)
+    assert eng._types_list == [0, 1, 1, 0, 1, 1, 1, 0, 0, 2]
+    _start(eng)
+    fake = fake_backend.instances[0]
+    assert composed == [(2, 10, 3)] and fake.n == 10
+    np.testing.assert_allclose(fake.ext, _expect_ext(eng, {1: F_A, 0: F_B}), rtol=1e-6, atol=0)
+    assert np.all(fake.ext[:, 9] == 0.0) and np.all(fake.ext[:, :9] != 0.0)
+
+
+def test_ext_force_on_an_unknown_type_raises(fake_backend, composed, tmp_path):
+    """espresso.py:846-850: no particle of the type."""
+    eng = _two_type_engine(tmp_path)
+    with pytest.raises(ValueError, match="Particles of type 7 not added to engine. "
+                                         "You currently have"):
+        eng.add_const_force_to_colloids(_force(eng, F_A), 7)
+    _start(eng)
+    with pytest.raises(ValueError, match="Particles of type 7 not added to engine"):
+        eng.add_const_force_to_colloids(_force(eng, F_A), 7)
+    # the refused calls left nothing behind
+    assert composed == [] and eng._ext_force == {}
+    assert "swarm_engine_set_external_force" not in [c[0] for c in fake_backend.instances[0].calls]
 
 
 def test_placement_matches_reference_draw_order(tmp_path):

@@ -314,6 +314,155 @@ def test_overlap_removal_separates(oracle_mod):
     assert steps <= 1000
 
 
+# ------------------------------- external force (espresso.py:834-851, ext_force)
+EXT_SPECIES = [(1.0, 4.6595, 6.2126, 1.0, 1.0), (0.7, 3.2617, 2.1309, 1.0, 1.0)]
+
+
+def _nonzero_forces(rng, shape, lo, hi):
+    """Random values of either sign with lo <= |x| < hi (never zero), as the
+    fp32 numbers the oracle takes."""
+    return (rng.uniform(lo, hi, shape) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
+
+
+@pytest.mark.parametrize("dims", [2, 3])
+def test_bd_kt0_external_force_drift_closed_form(oracle_mod, dims):
+    """kT = 0, no WCA, six isolated swimmers of two species with a constant
+    external force: after n sub-steps dx = n dt (f_ext + f_swim d) / gamma_t
+    per axis, and the velocity is (f_ext + f_swim d) / gamma_t.  In 2-D the z
+    component of f_ext moves nothing and vel[2] = 0; in 3-D z moves too.
+
+    Bound: |dx - expected| <= n sx / 2 + 4 2^-24 |expected|, sx = L / 2^32:
+    every sub-step rounds its displacement to one fixed-point unit (a
+    constant force rounds the same way every step), and the fp32 chain from
+    the force to the displacement has a handful of roundings of 2^-24 each.
+    Measured (L = 100, dt = 0.01, n = 100, forces of 1 to 8): the worst
+    |dx - expected| / bound is 0.85 in 2-D (1.23e-6 um against 1.44e-6) and
+    0.72 in 3-D (1.03e-6 um).
+    Velocities: the chain f_swim d, + f_ext, * (1 / gamma_t) is three fp32
+    roundings and the fp32 value of 1 / gamma_t a fourth, 2^-24 relative each
+    on terms no larger than (|f_ext| + |f_swim|) / gamma_t; the director's
+    fp32 sine and cosine (2-D: 2e-7 absolute, test_elementary_functions_
+    accuracy) add 2e-7 |f_swim| / gamma_t.  Measured: at most 0.20 of that
+    bound in 2-D and 0.35 in 3-D."""
+    L, dt, n_steps, n = 100.0, 0.01, 100, 6
+    box = [L, L, L]
+    rng = np.random.default_rng(71 + dims)
+    p = oracle_mod.make_params(box, dt, 0.0, 0.0, 3, EXT_SPECIES, n_dims=dims)
+    sp = np.array([0, 1, 0, 1, 1, 0])
+    gt = np.array([EXT_SPECIES[s][1] for s in sp])
+    pos = np.zeros((n, 3))
+    pos[:, :dims] = 20.0 + 20.0 * np.stack(np.unravel_index(np.arange(n), (3, 2, 1)), 1)[:, :dims]
+    pos[:, :dims] += rng.uniform(-1.0, 1.0, (n, dims))
+    f_swim = rng.uniform(1.0, 5.0, n).astype(np.float32)
+    f_ext = _nonzero_forces(rng, (3, n), 1.0, 8.0)
+    if dims == 2:
+        ang = rng.uniform(0.1, 1.4, n) + np.pi / 2 * rng.integers(0, 4, n)  # off the axes
+        dirs = np.stack([np.cos(ang), np.sin(ang), np.zeros(n)], 1)
+        st = oracle_mod.state_from_positions(pos, dirs, box)
+        st1, vel, _ = oracle_mod.bd_run(p, st, sp, f_swim, np.zeros(n), n_steps, f_ext=f_ext)
+        th = st["ang"].astype(np.float64) * (2 * np.pi / 2.0**32)
+        d = np.stack([np.cos(th), np.sin(th), np.zeros(n)])  # the director the oracle holds
+        sincos_err = 2e-7
+    else:
+        dirs = _nonzero_forces(rng, (n, 3), 0.3, 1.0)
+        st = oracle_mod.state3_from_positions(pos, dirs, box)
+        st1, vel, _ = oracle_mod.bd_run3(p, st, sp, f_swim, np.zeros((3, n)), n_steps,
+                                         f_ext=f_ext)
+        d = st["dir"].astype(np.float64)
+        assert np.array_equal(st1["dir"], st["dir"])  # no torque: the director stays
+        sincos_err = 0.0
+    force = f_ext.astype(np.float64) + f_swim.astype(np.float64) * d  # [3, n]
+    if dims == 2:
+        force[2] = 0.0
+    expect = (n_steps * dt * force / gt).T
+    dx = oracle_mod.unwrapped(st1, box, dims=3) - oracle_mod.unwrapped(st, box, dims=3)
+    bound = n_steps * (L / 2.0**32) / 2 + 4 * 2.0**-24 * np.abs(expect)
+    err = np.abs(dx - expect)
+    print("drift: worst |dx - expected| / bound", np.max(err / bound), "abs", err.max())
+    assert np.all(err <= bound), (err.max(), bound.min())
+    # the external force's share of every moving coordinate is far above the bound
+    assert np.all(n_steps * dt * np.abs(f_ext[:dims]) / gt > 1e4 * bound.T[:dims])
+    v_expect = force / gt
+    v_bound = (4 * 2.0**-24 * (np.abs(f_ext) + f_swim) + sincos_err * f_swim) / gt
+    v_err = np.abs(vel - v_expect)
+    print("drift: worst velocity error / bound", np.max(v_err / v_bound))
+    assert np.all(v_err <= v_bound)
+    if dims == 2:
+        assert np.all(dx[:, 2] == 0.0) and np.all(vel[2] == 0.0)
+        assert np.array_equal(st1["q"][2], st["q"][2]) and np.array_equal(st1["img"][2],
+                                                                         st["img"][2])
+    else:
+        assert np.all(dx[:, 2] != 0.0)
+
+
+@pytest.mark.parametrize("dims", [2, 3])
+def test_sd_external_force_step_is_clamped_gamma_f(oracle_mod, dims):
+    """Steepest descent with f_ext alone (no WCA, no swim force): every step
+    moves each coordinate by clamp(gamma f_ext, +-max_disp).  gamma = 0.1,
+    max_disp = 0.1: forces below 1 move by gamma F, larger ones by max_disp.
+    Bound per coordinate after n steps: n sx / 2 (the fixed-point rounding of
+    each step) + 3 2^-24 |expected| (gamma in fp32, gamma F, and the product
+    with 1 / sx)."""
+    L, n_steps, n = 100.0, 20, 8
+    box = [L, L, L]
+    rng = np.random.default_rng(81 + dims)
+    p = oracle_mod.make_params(box, 0.01, 0.0, 0.0, 3, EXT_SPECIES, n_dims=dims)
+    sp = np.arange(n) % 2
+    pos = np.zeros((n, 3))
+    pos[:, :dims] = 10.0 + 80.0 * rng.random((n, dims))
+    f_ext = _nonzero_forces(rng, (3, n), 0.05, 0.9)
+    f_ext[:, n // 2:] = _nonzero_forces(rng, (3, n - n // 2), 1.5, 30.0)  # clamped
+    dirs = np.tile([0.6, 0.8, 0.0], (n, 1))
+    if dims == 2:
+        st = oracle_mod.state_from_positions(pos, dirs, box)
+        st1, steps = oracle_mod.sd_run(p, st, sp, n_steps, f_ext=f_ext)
+    else:
+        st = oracle_mod.state3_from_positions(pos, dirs, box)
+        st1, steps = oracle_mod.sd_run3(p, st, sp, n_steps, f_ext=f_ext)
+    assert steps == n_steps
+    expect = (n_steps * np.clip(0.1 * f_ext.astype(np.float64), -0.1, 0.1)).T
+    if dims == 2:
+        expect[:, 2] = 0.0
+    assert np.any(np.abs(expect) == n_steps * 0.1) and np.any(np.abs(expect) < n_steps * 0.09)
+    dx = oracle_mod.unwrapped(st1, box, dims=3) - oracle_mod.unwrapped(st, box, dims=3)
+    bound = n_steps * (L / 2.0**32) / 2 + 3 * 2.0**-24 * np.abs(expect)
+    assert np.all(np.abs(dx - expect) <= bound), np.max(np.abs(dx - expect) / bound)
+    if dims == 2:
+        assert np.all(dx[:, 2] == 0.0)
+    key = "dir" if dims == 3 else "ang"
+    assert np.array_equal(st1[key], st[key])  # no torque: nothing turns
+
+
+def test_cell_list_equals_brute_force_with_external_force(oracle_mod):
+    """use_cells True and False give the same bits with f_ext in a dense box
+    (BD and steepest descent), and f_ext changes the trajectory."""
+    rng = np.random.default_rng(12)
+    box = [60.0, 60.0, 60.0]
+    n = 300
+    pos = np.zeros((n, 3))
+    pos[:, :2] = rng.random((n, 2)) * 60
+    ang = rng.random(n) * 2 * np.pi
+    dirs = np.stack([np.cos(ang), np.sin(ang), 0 * ang], 1)
+    p = oracle_mod.make_params(box, 1e-3, 1.02, 1.02, 9,
+                               [(1.0, 4.66, 6.2, 1e-6, 4e-7), (0.7, 3.3, 2.1, 1e-6, 4e-7)])
+    sp = rng.integers(0, 2, n).astype(np.uint8)
+    st = oracle_mod.state_from_positions(pos, dirs, box)
+    f_ext = (rng.normal(size=(3, n)) * 4).astype(np.float32)
+    f, t = np.full(n, 3.0), np.full(n, 0.5)
+    a, va, _ = oracle_mod.bd_run(p, st, sp, f, t, 25, f_ext=f_ext, use_cells=True)
+    b, vb, _ = oracle_mod.bd_run(p, st, sp, f, t, 25, f_ext=f_ext, use_cells=False)
+    for k in a:
+        assert np.array_equal(a[k], b[k])
+    assert np.array_equal(va, vb)
+    assert len(oracle_mod.neighbor_pairs(p, a, 2.0)) > 10  # the box is dense: pairs in contact
+    none, _, _ = oracle_mod.bd_run(p, st, sp, f, t, 25)
+    assert not np.array_equal(none["q"], a["q"])
+    c, _ = oracle_mod.sd_run(p, st, sp, 25, f_ext=f_ext, use_cells=True)
+    d, _ = oracle_mod.sd_run(p, st, sp, 25, f_ext=f_ext, use_cells=False)
+    for k in c:
+        assert np.array_equal(c[k], d[k])
+
+
 # ------------------------------------------------ schedule (test_integration.py)
 @pytest.mark.parametrize(
     "slice_, write, calls, expect",

@@ -136,6 +136,36 @@ def test_add_rod_refuses_walls(tmp_path):
         runner.integrate(1, ForceFunction({"0": dummy_models.ConstForce(0)}))
 
 
+def test_rod_refuses_a_constant_force_on_its_type(tmp_path):
+    """k_rod_run applies f_ext to the free colloids only, so a force on the
+    rod's type would be dropped without a word: the host refuses it, whether
+    the rod or the colloids' force came first.  A force on the colloids' type
+    is fine, and its rows for the rod's particles are zero."""
+    ureg, runner = _runner(tmp_path / "a")
+    force = ureg.Quantity(np.array([1.0, 2.0, 0.0]), "sim_force")
+    runner.add_rod(**_rod_args(ureg))
+    with pytest.raises(NotImplementedError, match="rod's type"):
+        runner.add_const_force_to_colloids(force, 2)
+    assert runner._ext_force == {}
+    runner.add_const_force_to_colloids(force, 0)
+
+    ureg, runner = _runner(tmp_path / "b")
+    force = ureg.Quantity(np.array([1.0, 2.0, 0.0]), "sim_force")
+    runner.add_const_force_to_colloids(force, 0)
+    with pytest.raises(ValueError, match="Particles of type 2 not added"):
+        runner.add_const_force_to_colloids(force, 2)  # (no rod yet: the reference's error)
+    runner.add_rod(**_rod_args(ureg))
+    with pytest.raises(NotImplementedError, match="rod's type"):
+        runner.add_const_force_to_colloids(force, 2)
+    ext = runner._compose_ext_force()
+    assert ext.shape == (1, 81, 3)
+    assert np.all(ext[0, :50] == [1.0, 2.0, 0.0]) and np.all(ext[0, 50:] == 0.0)
+    # the check of the first integrate: a force that got onto the rod's type some other way
+    runner._ext_force[2] = np.zeros(3)
+    with pytest.raises(NotImplementedError, match="rod's type"):
+        runner._validate_rod()
+
+
 def test_add_rod_refuses_a_non_periodic_box(tmp_path):
     ureg, runner = _runner(tmp_path, periodic=False)
     with pytest.raises(NotImplementedError, match="non-periodic"):
@@ -396,6 +426,66 @@ def test_restatement_central_push_translates_without_turning():
     assert dy > 0 and st["q"][0, c] == st0["q"][0, c]
     # every bead moved with the centre
     assert np.array_equal(st["q"][1, c:].astype(np.int64) - st0["q"][1, c:], np.full(rod.n, dy))
+
+
+def test_restatement_external_force_moves_the_colloids_only():
+    """f_ext in the rod restatement.  Free colloids far from the rod at kT = 0
+    drift by n dt (f_ext + f_swim d) / gamma_t (the bound of
+    test_oracle_kat.py's drift case: n sx / 2 + 4 2^-24 |expected|), the z
+    component moves nothing, and the rod keeps its bits.  In a contact run
+    at kT > 0 a force on the rod's own particles has no effect: the same bits
+    as zeros there -- what k_rod_run does, which skips f_ext for the rod."""
+    rng = np.random.default_rng(8)
+    cpos = np.array([[8.0, 9.0], [41.0, 10.0], [9.0, 40.0], [42.0, 41.0]])
+    ang = np.array([0.4, 2.0, 3.7, 5.5])
+    params, st0, species, rod = _system(cpos, np.stack([np.cos(ang), np.sin(ang)], 1), angle=0.3)
+    n, nc, n_steps = len(species), len(cpos), 100
+    f_swim = np.array([2.0, 3.0, 1.5, 4.0] + rod.n * [0.0], np.float32)
+    f_ext = (rng.uniform(1.0, 6.0, (3, n)) * rng.choice([-1.0, 1.0], (3, n))).astype(np.float32)
+    st, info = rod_oracle.bd_run(params, st0, species, f_swim, np.zeros(n), n_steps, rod,
+                                 f_ext=f_ext)
+    assert info["contacts"] == 0
+    th = st0["ang"][:nc].astype(np.float64) * (2 * np.pi / 2.0**32)
+    force = f_ext[:2, :nc].astype(np.float64) + f_swim[:nc] * np.stack([np.cos(th), np.sin(th)])
+    expect = (n_steps * DT * force / COLLOID[1]).T
+    dx = (oracle.unwrapped(st, BOX) - oracle.unwrapped(st0, BOX))[:nc]
+    bound = n_steps * (BOX[0] / 2.0**32) / 2 + 4 * 2.0**-24 * np.abs(expect)
+    assert np.all(np.abs(dx[:, :2] - expect) <= bound), np.max(np.abs(dx[:, :2] - expect) / bound)
+    assert np.all(dx[:, 2] == 0.0) and np.all(info["vel"][2] == 0.0)
+    v_bound = (4 * 2.0**-24 * (np.abs(f_ext[:2, :nc]) + f_swim[:nc]) + 2e-7 * f_swim[:nc])
+    assert np.all(np.abs(info["vel"][:2, :nc] - force / COLLOID[1]) <= v_bound / COLLOID[1])
+    c = rod.first
+    for k in ("q", "img", "ang"):  # kT = 0, no contact: the forced rod does not move
+        assert np.array_equal(st[k][..., c:], st0[k][..., c:])
+
+    # contacts, noise, a free rod: the rod's rows of f_ext are never read
+    th = np.linspace(0.0, 2 * np.pi, 12, endpoint=False)
+    ring = 25.0 + np.stack([9.0 * np.cos(th), 2.6 * np.sin(th)], axis=1)
+    facing = np.stack([-np.cos(th), -np.sin(th)], axis=1)
+    params, st0, species, rod = _system(ring + rng.uniform(-0.05, 0.05, ring.shape), facing,
+                                        angle=0.1, kT=1.0, fixed=False)
+    n = len(species)
+    f_swim = np.array(12 * [6.0] + rod.n * [0.0], np.float32)
+    f_ext = (rng.normal(size=(3, n)) * 3).astype(np.float32)
+    zeroed = f_ext.copy()
+    zeroed[:, rod.first:] = 0.0
+    a, ia = rod_oracle.bd_run(params, st0, species, f_swim, np.zeros(n), 30, rod, f_ext=f_ext)
+    b, ib = rod_oracle.bd_run(params, st0, species, f_swim, np.zeros(n), 30, rod, f_ext=zeroed)
+    none, _ = rod_oracle.bd_run(params, st0, species, f_swim, np.zeros(n), 30, rod)
+    assert ia["contacts"] >= 10
+    for k in ("q", "img", "ang"):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(ia["vel"], ib["vel"]) and np.array_equal(ia["omega"], ib["omega"])
+    assert np.array_equal(ia["F"], ib["F"]) and ia["tau"] == ib["tau"]
+    assert not np.array_equal(a["q"], none["q"])
+    # the overlap removal: the same holds
+    sa, _ = rod_oracle.sd_run(params, st0, species, 50, rod, f_ext=f_ext)
+    sb, _ = rod_oracle.sd_run(params, st0, species, 50, rod, f_ext=zeroed)
+    s0, _ = rod_oracle.sd_run(params, st0, species, 50, rod)
+    for k in ("q", "img", "ang"):
+        assert np.array_equal(sa[k], sb[k]), k
+        assert np.array_equal(sa[k][..., rod.first:], st0[k][..., rod.first:])
+    assert not np.array_equal(sa["q"], s0["q"])
 
 
 def test_restatement_overlap_removal_keeps_the_rod():
