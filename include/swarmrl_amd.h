@@ -204,6 +204,25 @@ int swarm_engine_download_directors(swarm_engine_t *e, float *dir3);
 int swarm_engine_set_walls(swarm_engine_t *e, const swarm_wall_t *walls,
                            int32_t n_walls);
 
+/* Gridded external potential; replaces add_external_potential
+ * (espresso.py:995-1036: np.pad(mode="wrap") + constraints.PotentialField).
+ * phi is host fp32 [nx][ny][nz] in simulation energy units (copied), value
+ * [i][j][k] at the cell centre ((i + .5) hx, (j + .5) hy, (k + .5) hz);
+ * spacing = {hx, hy, hz}.  The field is periodic and interpolated
+ * (tri)linearly; the force, minus the interpolant's gradient at the
+ * particle's folded position, is added to the external force of every
+ * particle in every BD sub-step and overlap-removal step (fixed fp32
+ * sequence: swarm_potential.cuh).  Replaces a previous field; phi = NULL
+ * removes it (the other arguments are then ignored).  SWARM_EINVAL for a
+ * count < 1, a non-finite value or spacing, nz != 1 on a 2-D engine,
+ * n_a h_a differing from the box length by more than 1e-9 relative, more
+ * than 2^31 - 1 stored values (a 2-D engine stores four per cell), or an
+ * engine with a rod.  Moves no particle: a
+ * pending build stays valid. */
+int swarm_engine_set_potential_field(swarm_engine_t *e, const float *phi,
+                                     int32_t nx, int32_t ny, int32_t nz,
+                                     const double *spacing);
+
 /* Number of (particle, sub-step) wall contacts with dist <= 0 since the
  * engine was created (ESPResSo raises for those; synchronous). */
 int swarm_engine_wall_violations(swarm_engine_t *e, uint64_t *count);

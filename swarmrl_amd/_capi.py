@@ -301,6 +301,10 @@ _SIGNATURES = {
     "swarm_engine_upload_directors": (ctypes.c_int, [_P, _P]),
     "swarm_engine_download_directors": (ctypes.c_int, [_P, _P]),
     "swarm_engine_set_walls": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
+    "swarm_engine_set_potential_field": (
+        ctypes.c_int,
+        [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P],
+    ),
     "swarm_engine_wall_violations": (ctypes.c_int, [_P, _P]),
     "swarm_engine_set_rod": (ctypes.c_int, [_P, ctypes.POINTER(SwarmRod)]),
     "swarm_rod_reward": (

@@ -1494,6 +1494,10 @@ struct swarm_engine {
   // swarm_engine_set_rod: every sub-step runs on k_rod_run (swarm_rod.cuh)
   bool has_rod = false;
   swarm::RodArgs rod{};
+  // swarm_engine_set_potential_field: the field's device copy (derived.pot.phi
+  // points at it while a field is set) and its capacity in values
+  float* d_pot = nullptr;
+  size_t pot_cap = 0;
   void* allocs[96] = {};
   int n_allocs = 0;
 };
@@ -1576,6 +1580,10 @@ void set_lds_attributes() {
                        reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<true, false>),
                        reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<false, true>),
                        reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<true, true>),
+                       reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<false, false, true>),
+                       reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<true, false, true>),
+                       reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<false, true, true>),
+                       reinterpret_cast<const void*>(&swarm::k_cluster_run_wide<true, true, true>),
                        reinterpret_cast<const void*>(&k_vgrid_sort<4>),
                        reinterpret_cast<const void*>(&k_vgrid_sort<16>),
                        reinterpret_cast<const void*>(&k_field_vgrid_sort<4>),
@@ -1774,6 +1782,7 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
   const long waves = (long)e->n_envs * e->sc.wmax;
   const bool multi = e->params.n_species > 1;
   const bool walls = e->derived.n_walls != 0;
+  const bool pot = e->derived.pot.phi != nullptr;  // swarm_engine_set_potential_field
   if (e->wide_run) {
     // dynamic LDS beyond half a CU's keeps one block (run_wpb run waves) per CU
     const int R = e->run_wpb;
@@ -1785,10 +1794,17 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
     const int helpers = e->rot_helper && R <= 2 ? 1 : 0;
     const size_t lds = helpers ? std::max<size_t>(96 * 1024, R * swarm::helper_lds_bytes())
                                : 96 * 1024;
-#define SWARM_WIDE(MULTI, WALLS)                                                             \
-  hipLaunchKernelGGL((swarm::k_cluster_run_wide<MULTI, WALLS>), grid, dim3(1024), lds, e->stream, \
-                     e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step, e->d_noise,      \
-                     e->noise_blocks, R, ncb, e->lxb, e->lyb, tstamp, helpers)
+#define SWARM_WIDE_P(MULTI, WALLS, POT)                                                      \
+  hipLaunchKernelGGL((swarm::k_cluster_run_wide<MULTI, WALLS, POT>), grid, dim3(1024), lds,      \
+                     e->stream, e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step,       \
+                     e->d_noise, e->noise_blocks, R, ncb, e->lxb, e->lyb, tstamp, helpers)
+#define SWARM_WIDE(MULTI, WALLS)         \
+  do {                                   \
+    if (pot)                             \
+      SWARM_WIDE_P(MULTI, WALLS, true);  \
+    else                                 \
+      SWARM_WIDE_P(MULTI, WALLS, false); \
+  } while (0)
     if (walls) {
       if (multi)
         SWARM_WIDE(true, true);
@@ -1801,6 +1817,7 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
         SWARM_WIDE(false, false);
     }
 #undef SWARM_WIDE
+#undef SWARM_WIDE_P
     e->next_table_ready = e->noise_blocks > 0;
   } else {
     // XCD-aware env placement (swarm::xcd_env_block) once the envs fill the
@@ -1810,10 +1827,17 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
     const bool xcd = E >= 8 && (E % 8 == 0 || E >= 64);
     const dim3 run_grid((unsigned)(xcd ? 8 * ((E + 7) / 8) * bpe : (waves + 3) / 4)),
         run_block(256);
-#define SWARM_RUN(MULTI, TABLE, WALLS)                                                     \
-  hipLaunchKernelGGL((swarm::k_cluster_run<MULTI, TABLE, WALLS>), run_grid, run_block, 0,   \
-                     e->stream, e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step,  \
+#define SWARM_RUN_P(MULTI, TABLE, WALLS, POT)                                                   \
+  hipLaunchKernelGGL((swarm::k_cluster_run<MULTI, TABLE, WALLS, POT>), run_grid, run_block, 0, \
+                     e->stream, e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step,     \
                      e->d_noise, xcd ? bpe : 0, tstamp)
+#define SWARM_RUN(MULTI, TABLE, WALLS)         \
+  do {                                         \
+    if (pot)                                   \
+      SWARM_RUN_P(MULTI, TABLE, WALLS, true);  \
+    else                                       \
+      SWARM_RUN_P(MULTI, TABLE, WALLS, false); \
+  } while (0)
 #define SWARM_RUN_W(MULTI, TABLE)      \
   do {                                 \
     if (walls)                         \
@@ -1834,6 +1858,7 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
     }
 #undef SWARM_RUN_W
 #undef SWARM_RUN
+#undef SWARM_RUN_P
     e->next_table_ready = false;
   }
   HIP_TRY(hipGetLastError());
@@ -1951,9 +1976,16 @@ int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_rea
     // one wave per block (so per CU) while the waves fit the chip, else four
     const int tpb = waves <= 256 ? 64 : 256;
     const dim3 grid((unsigned)((waves * 64 + tpb - 1) / tpb));
-#define SWARM_RUN3(MULTI, WALLS)                                                              \
-  hipLaunchKernelGGL((swarm::k_cluster_run3<MULTI, WALLS>), grid, dim3(tpb), 0, e->stream,     \
+#define SWARM_RUN3_P(MULTI, WALLS, POT)                                                        \
+  hipLaunchKernelGGL((swarm::k_cluster_run3<MULTI, WALLS, POT>), grid, dim3(tpb), 0, e->stream, \
                      e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step)
+#define SWARM_RUN3(MULTI, WALLS)         \
+  do {                                   \
+    if (e->derived.pot.phi)              \
+      SWARM_RUN3_P(MULTI, WALLS, true);  \
+    else                                 \
+      SWARM_RUN3_P(MULTI, WALLS, false); \
+  } while (0)
     if (walls) {
       if (multi)
         SWARM_RUN3(true, true);
@@ -1966,6 +1998,7 @@ int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_rea
         SWARM_RUN3(false, false);
     }
 #undef SWARM_RUN3
+#undef SWARM_RUN3_P
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(swarm::k_check3, dim3(e->n_envs), dim3(1024), check3_lds_bytes(e), e->stream,
                        e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg,
@@ -2463,6 +2496,7 @@ void swarm_engine_destroy(swarm_engine_t* e) {
   for (int k = 0; k < e->n_allocs; ++k) (void)hipFree(e->allocs[k]);
   if (e->d_start) (void)hipFree(e->d_start);
   if (e->d_pairs) (void)hipFree(e->d_pairs);
+  if (e->d_pot) (void)hipFree(e->d_pot);
   if (e->traj_host) (void)hipHostFree(e->traj_host);
   if (e->d_traj_count) (void)hipFree(e->d_traj_count);
   delete e;
@@ -3727,6 +3761,89 @@ int swarm_engine_set_walls(swarm_engine_t* e, const swarm_wall_t* walls, int32_t
   return SWARM_OK;
 }
 
+// Gridded external potential (espresso.py:995-1036): the host field is
+// copied to the device and described in Derived::pot; every
+// integrator path but the rod kernel reads it (swarm_potential.cuh).  Like
+// swarm_engine_set_walls it moves no particle, so a pending build stays valid.
+int swarm_engine_set_potential_field(swarm_engine_t* e, const float* phi, int32_t nx, int32_t ny,
+                                     int32_t nz, const double* spacing) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  Derived& d = e->derived;
+  if (!phi) {  // remove the field (the device copy is kept for a later one)
+    d.pot = swarm::PotentialField{};
+  } else {
+    if (!spacing) return fail(SWARM_EINVAL, "null spacing");
+    if (e->has_rod) return fail(SWARM_EINVAL, "a potential with a rod is not supported");
+    const int32_t n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a)
+      if (n[a] < 1) return fail(SWARM_EINVAL, "grid counts must be positive");
+    if (e->params.n_dims == 2 && nz != 1)
+      return fail(SWARM_EINVAL, "a 2-D engine takes a potential with nz = 1");
+    const uint64_t count = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    // 2-D: one record of its four corners per cell (swarm_potential.cuh)
+    const bool records = e->params.n_dims == 2;
+    const uint64_t words = records ? 4 * count : count;
+    if ((uint64_t)nx * (uint64_t)ny > 0x7fffffffull || words > 0x7fffffffull)
+      return fail(SWARM_EINVAL, "potential grid too large (32-bit indexing)");
+    for (int a = 0; a < 3; ++a) {
+      const double h = spacing[a], L = e->params.box[a];
+      if (!std::isfinite(h) || !(h > 0.0)) return fail(SWARM_EINVAL, "grid spacing must be positive");
+      if (!(std::fabs(n[a] * h - L) <= 1e-9 * L))
+        return fail(SWARM_EINVAL, "the potential grid must tile the box");
+    }
+    for (uint64_t k = 0; k < count; ++k)
+      if (!std::isfinite(phi[k])) return fail(SWARM_EINVAL, "non-finite potential value");
+    std::vector<float> rec;
+    if (records) {
+      rec.resize((size_t)words);
+      for (int32_t i = 0; i < nx; ++i) {
+        const size_t r0 = (size_t)i * ny, r1 = (size_t)((i + 1) % nx) * ny;
+        for (int32_t j = 0; j < ny; ++j) {
+          const size_t j1 = (size_t)((j + 1) % ny);
+          float* o = &rec[4 * (r0 + j)];
+          o[0] = phi[r0 + j];
+          o[1] = phi[r1 + j];
+          o[2] = phi[r0 + j1];
+          o[3] = phi[r1 + j1];
+        }
+      }
+    }
+    if (words > e->pot_cap) {
+      // the new copy first: a failed allocation leaves the old field in place
+      void* v = nullptr;
+      HIP_TRY(hipMalloc(&v, words * sizeof(float)));
+      if (e->d_pot) {
+        // no kernel may find the old copy once it is freed: the device's
+        // descriptor is cleared first, and the stream drained of its readers
+        d.pot = swarm::PotentialField{};
+        hipError_t err = hipMemcpyAsync(e->d_derived, &e->derived, sizeof(Derived),
+                                        hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+        if (err == hipSuccess) err = hipFree(e->d_pot);
+        if (err != hipSuccess) {
+          (void)hipFree(v);
+          return fail(SWARM_EDEVICE, std::string("potential field: ") + hipGetErrorString(err));
+        }
+      }
+      e->d_pot = reinterpret_cast<float*>(v);
+      e->pot_cap = (size_t)words;
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_pot, records ? rec.data() : phi, words * sizeof(float),
+                           hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (rec is a local)
+    d.pot.phi = e->d_pot;
+    for (int a = 0; a < 3; ++a) {
+      d.pot.n[a] = n[a];
+      d.pot.inv_h[a] = (float)(1.0 / spacing[a]);
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_derived, &e->derived, sizeof(Derived), hipMemcpyHostToDevice,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
 int swarm_engine_wall_violations(swarm_engine_t* e, uint64_t* count) {
   if (!e || !count) return fail(SWARM_EINVAL, "null argument");
   if (const int frc = flush_check(e)) return frc;
@@ -3744,6 +3861,7 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "Rod can only be added in 2d");
   if (!e->params.periodic) return fail(SWARM_EINVAL, "a rod needs a periodic box");
   if (e->derived.n_walls) return fail(SWARM_EINVAL, "a rod with walls is not supported");
+  if (e->derived.pot.phi) return fail(SWARM_EINVAL, "a rod with a potential is not supported");
   if (rod->n < 1 || rod->n % 2 != 1) return fail(SWARM_EINVAL, "n_particles must be uneven");
   if (rod->n > swarm::kRodMaxParticles)
     return fail(SWARM_ECAPACITY, "a rod has at most 255 particles");

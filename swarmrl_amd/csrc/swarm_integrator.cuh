@@ -36,6 +36,7 @@
 
 #include "../../include/swarmrl_amd.h"
 #include "swarm_device.cuh"
+#include "swarm_potential.cuh"
 
 // Sub-step schedule of the run kernels (round 6): off-chain work placed in
 // the latency windows of the position exchange and the force-sum round trip.
@@ -55,6 +56,12 @@ constexpr int kMaxSpecies = SWARM_MAX_SPECIES;
 // k_cluster_run: 5 blocks (waves) per CU (SIMD), so <= 96 VGPRs (the 24 B/lane
 // spill this costs measured cheaper than 4 waves per SIMD)
 constexpr int kRunMinBlocks = 5;
+// its variants with a potential (kPot): 4, so <= 128 VGPRs and no spill
+// (measured against 5 with its spill, DESIGN.md §10 "External potential")
+#ifndef SWARM_POT_MIN_BLOCKS
+#define SWARM_POT_MIN_BLOCKS 4
+#endif
+constexpr int kRunMinBlocksPot = SWARM_POT_MIN_BLOCKS;
 constexpr int kMaxWindow = 128;   // sub-steps per cluster window
 constexpr int kPairsPerWave = 256;  // neighbour pairs of one 64-lane wave (4 passes)
 // Clusters wider than a wave ("big" clusters) run in k_check's workgroup, one
@@ -113,6 +120,8 @@ struct Derived {
   int32_t wkind[SWARM_MAX_WALLS];
   float wp[SWARM_MAX_WALLS][8];
   float wcut2[kMaxSpecies], wsig6[kMaxSpecies];  // wall WCA per species (radius 0 wall)
+  // gridded external potential (swarm_engine_set_potential_field); phi null: none
+  PotentialField pot;
 };
 
 struct DevState {
@@ -890,7 +899,13 @@ __device__ void block_global_run(const Derived* __restrict__ d, const DevState& 
       const bool first = st.reuse && s == 0 && !sd_mode;  // reuse_forces: previous run's
       const float fs = first ? prv.f[gi] : st.f_swim[gi];
       const float tz = first ? prv.tz[gi] : st.torque_z[gi];
-      const float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+      float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+      if (d->pot.phi) {  // the field at the folded position, every sub-step
+        float F[3];
+        potential_force<2>(d->pot, p.qx, p.qy, 0u, F);
+        fex = fex + F[0];
+        fey = fey + F[1];
+      }
       const PConst pc = load_pconst(d, si);
       if (sd_mode) {
         any |= sd_step(pc, p, ax, ay, fs, tz, fex, fey, g, md) ? 1 : 0;
@@ -1012,7 +1027,13 @@ __device__ __forceinline__ void block_global_run_lds(const Derived* __restrict__
       const bool first = st.reuse && s == 0 && !sd_mode;  // reuse_forces: previous run's
       const float fs = first ? prv.f[gi] : st.f_swim[gi];
       const float tz = first ? prv.tz[gi] : st.torque_z[gi];
-      const float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+      float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+      if (d->pot.phi) {  // (the loads land while the pair sums run)
+        float F[3];
+        potential_force<2>(d->pot, pp.qx, pp.qy, 0u, F);
+        fex = fex + F[0];
+        fey = fey + F[1];
+      }
       int64_t ax = 0, ay = 0;
       const int c0 = cell_index(pp.qx, pp.qy, lx, ly);
       const int cx = c0 & (ncx - 1), cy = c0 >> lx;
@@ -3294,7 +3315,10 @@ __device__ __forceinline__ void lds_sub_u64_xy(unsigned long long* px, unsigned 
                    : "memory");
 }
 
-template <bool kMulti, bool kTable, bool kWalls, bool kTwoPass = false, bool kHelper = false>
+// kPot (host-chosen, as kWalls): the engine has a gridded potential
+// (Derived::pot); without it the sub-step is exactly the plain one.
+template <bool kMulti, bool kTable, bool kWalls, bool kTwoPass = false, bool kHelper = false,
+          bool kPot = false>
 __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const DevState& st,
                                          const Scratch& sc, int n_envs, int n_steps,
                                          uint64_t step0, const float* __restrict__ table,
@@ -3373,6 +3397,10 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
   const float tz0 = tz, tzc = (kHelper && active) ? st.torque_z[gi] : 0.0f;
   Carry carry = {0u, 0u, 0, 0};  // the previous sub-step's image carries, pending
   const float cut2_0 = d->cut2[0], sig6_0 = d->sig6[0];
+  // kPot: the field's descriptor (wave-uniform scalars)
+  const float* const pot_phi = kPot ? d->pot.phi : nullptr;
+  const uint32_t pot_nx = kPot ? (uint32_t)d->pot.n[0] : 1u, pot_ny = kPot ? (uint32_t)d->pot.n[1] : 1u;
+  const float pot_ihx = kPot ? d->pot.inv_h[0] : 0.0f, pot_ihy = kPot ? d->pot.inv_h[1] : 0.0f;
   const uint32_t q0x = p.qx, q0y = p.qy;
   float dmax2 = 0.0f;
   float vx = 0.0f, vy = 0.0f, om = 0.0f;
@@ -3419,6 +3447,24 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       gn[2] = nx[2 * ts];
     }
     if (!kTable && pc.noisy) noise.next(k0, k1, (uint32_t)i, step0 + (uint64_t)s, s == 0, gt);
+    // kPot: the cell's four corners (one 16-byte record) at this sub-step's
+    // positions, loaded ahead of the pair exchange so the L2 round trip runs
+    // beside the pair chain (it is the longer of the two: DESIGN.md section
+    // 10, "External potential"; idle lanes read cell 0); fxe, fye: f_ext +
+    // field force (the throughput kernel, with other waves to cover the
+    // load, fetches where it combines and holds nothing across the pair loop)
+    PotSample2 psamp = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (kPot && kSched != 0) psamp = pot_fetch2(pot_phi, pot_nx, pot_ny, p.qx, p.qy);
+    float fxe = fex, fye = fey;
+    auto ext_force = [&]() __attribute__((always_inline)) {
+      if constexpr (kPot) {
+        if constexpr (kSched == 0) psamp = pot_fetch2(pot_phi, pot_nx, pot_ny, p.qx, p.qy);
+        float Fx, Fy;
+        pot_force2(psamp, pot_ihx, pot_ihy, &Fx, &Fy);
+        fxe = fex + Fx;
+        fye = fey + Fy;
+      }
+    };
     int64_t ax = 0, ay = 0;
     float dnext[2] = {dir[0], dir[1]};
     uint32_t an_next;
@@ -3573,6 +3619,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       }
       __builtin_amdgcn_sched_barrier(0);
       director();
+      ext_force();
       if (kHelper && SWARM_HELPER_WIN2) {
         // the round trip's latency window holds no rotation in helper mode:
         // the previous sub-step's displacement and image carries go here
@@ -3587,6 +3634,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       __builtin_amdgcn_sched_barrier(0);
       rotate();
       director();
+      ext_force();
       __builtin_amdgcn_sched_barrier(0);
       __asm__ volatile("" ::: "memory");  // keep the read-back after the director
       if (kPass > 0) {
@@ -3623,7 +3671,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       // (the last sub-step applies its own)
       const PState p0 = p;
       const bool fits = wave_all2(fits_i32(ax), fits_i32(ay));
-      bd_translate_f(pc, p, (float)(int32_t)ax, (float)(int32_t)ay, fs, tz, fex, fey, k0,
+      bd_translate_f(pc, p, (float)(int32_t)ax, (float)(int32_t)ay, fs, tz, fxe, fye, k0,
                            k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt, dir[0],
                            dir[1], kLast ? nullptr : &carry);
       // computed before the vote's branch (else the compiler moves the
@@ -3631,13 +3679,13 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       __asm__ volatile("" : "+v"(p.qx), "+v"(p.qy));
       if (__builtin_expect(!fits, 0)) {
         p = p0;
-        bd_translate_f(pc, p, i64_to_f32_wide(ax), i64_to_f32_wide(ay), fs, tz, fex, fey,
+        bd_translate_f(pc, p, i64_to_f32_wide(ax), i64_to_f32_wide(ay), fs, tz, fxe, fye,
                              k0, k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt,
                              dir[0], dir[1], kLast ? nullptr : &carry);
       }
     } else {
       // (the throughput kernel: the three-operation carry, advance_adc)
-      bd_translate(pc, p, ax, ay, fs, tz, fex, fey, k0, k1, (uint32_t)i, step0 + (uint64_t)s,
+      bd_translate(pc, p, ax, ay, fs, tz, fxe, fye, k0, k1, (uint32_t)i, step0 + (uint64_t)s,
                    kLast, &vx, &vy, &om, gt, dir[0], dir[1], kSched == 0);
     }
     if (!kSched || kLast) {  // (else the next sub-step's prev_disp)
@@ -3749,7 +3797,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
 
 // Uniform dispatch to the compile-time variants: normals from a table
 // (table != null) or drawn here; walls or none.
-template <bool kMulti, bool kWalls, bool kTwoPass = false>
+template <bool kMulti, bool kWalls, bool kTwoPass = false, bool kPot = false>
 __device__ __forceinline__ void run_wave_dispatch(const Derived* __restrict__ d, const DevState& st,
                                                   const Scratch& sc, int n_envs, int n_steps,
                                                   uint64_t step0, const float* __restrict__ table,
@@ -3760,14 +3808,16 @@ __device__ __forceinline__ void run_wave_dispatch(const Derived* __restrict__ d,
                                                   bool help = false, HelperLds hl = HelperLds{},
                                                   const float2* ntab = ntab_global()) {
   if (table && help)
-    run_wave<kMulti, true, kWalls, kTwoPass, true>(d, st, sc, n_envs, n_steps, step0, table, gw,
-                                                   lane, lacc_x, lacc_y, pt, par, hl);
+    run_wave<kMulti, true, kWalls, kTwoPass, true, kPot>(d, st, sc, n_envs, n_steps, step0, table,
+                                                         gw, lane, lacc_x, lacc_y, pt, par, hl);
   else if (table)
-    run_wave<kMulti, true, kWalls, kTwoPass>(d, st, sc, n_envs, n_steps, step0, table, gw, lane,
-                                             lacc_x, lacc_y, pt, par, HelperLds{}, ntab);
+    run_wave<kMulti, true, kWalls, kTwoPass, false, kPot>(d, st, sc, n_envs, n_steps, step0, table,
+                                                          gw, lane, lacc_x, lacc_y, pt, par,
+                                                          HelperLds{}, ntab);
   else
-    run_wave<kMulti, false, kWalls, kTwoPass>(d, st, sc, n_envs, n_steps, step0, nullptr, gw, lane,
-                                              lacc_x, lacc_y, pt, par, HelperLds{}, ntab);
+    run_wave<kMulti, false, kWalls, kTwoPass, false, kPot>(d, st, sc, n_envs, n_steps, step0,
+                                                           nullptr, gw, lane, lacc_x, lacc_y, pt,
+                                                           par, HelperLds{}, ntab);
 }
 
 // Launch-duration stamps for measurement (bench.py, swarm_engine_profile
@@ -3803,8 +3853,8 @@ __device__ __forceinline__ bool xcd_env_block(int b, int blocks_per_env, int n_e
 // xcd_bpe > 0: blocks placed by xcd_env_block with xcd_bpe blocks per env
 // (ceil(wmax / 4)); else block b runs waves 4 b .. 4 b + 3 of the env-major
 // wave list.
-template <bool kMulti, bool kTable, bool kWalls>
-__global__ __launch_bounds__(256, kRunMinBlocks) void k_cluster_run(const Derived* __restrict__ d, DevState st,
+template <bool kMulti, bool kTable, bool kWalls, bool kPot = false>
+__global__ __launch_bounds__(256, kPot ? kRunMinBlocksPot : kRunMinBlocks) void k_cluster_run(const Derived* __restrict__ d, DevState st,
                                                      Scratch sc, int n_envs, int n_steps,
                                                      const uint64_t* __restrict__ ctl,
                                                      const float* __restrict__ tables,
@@ -3834,10 +3884,10 @@ __global__ __launch_bounds__(256, kRunMinBlocks) void k_cluster_run(const Derive
   }
   // a table that does not cover this window (the device check; the host
   // normally guarantees it) -> the normals are drawn in the kernel
-  run_wave_dispatch<kMulti, kWalls>(d, st, sc, n_envs, n_steps, step0,
-                                    table_ok ? tables + par * noise_table_words(st.m) : nullptr,
-                                    gw, lane, lacc[wv][0], lacc[wv][1], pt, par, false,
-                                    HelperLds{}, ntab_lds);
+  run_wave_dispatch<kMulti, kWalls, false, kPot>(
+      d, st, sc, n_envs, n_steps, step0,
+      table_ok ? tables + par * noise_table_words(st.m) : nullptr, gw, lane, lacc[wv][0],
+      lacc[wv][1], pt, par, false, HelperLds{}, ntab_lds);
   stamp_end(tstamp);
 }
 
@@ -3849,7 +3899,7 @@ __global__ __launch_bounds__(256, kRunMinBlocks) void k_cluster_run(const Derive
 // run with waves [0, run_wpb) only: one run wave per CU at E = 1 (its
 // scattered noise-table gathers then have the CU's texture path to themselves),
 // up to one per SIMD for more envs.
-template <bool kMulti, bool kWalls>
+template <bool kMulti, bool kWalls, bool kPot = false>
 __global__ __launch_bounds__(1024) void k_cluster_run_wide(const Derived* __restrict__ d,
                                                            DevState st, Scratch sc, int n_envs,
                                                            int n_steps, uint64_t* __restrict__ ctl,
@@ -3930,8 +3980,8 @@ __global__ __launch_bounds__(1024) void k_cluster_run_wide(const Derived* __rest
   // latency-bound launches last as long as their slowest wave: one with
   // 65-128 pairs (a cluster denser than two pairs per particle) runs its own
   // unrolled two-pass sub-step instead of the general pass loop
-  run_wave_dispatch<kMulti, kWalls, true>(d, st, sc, n_envs, n_steps, step0, table, gw, lane,
-                                          lacc[wv][0], lacc[wv][1], pt, par, help, hl);
+  run_wave_dispatch<kMulti, kWalls, true, kPot>(d, st, sc, n_envs, n_steps, step0, table, gw, lane,
+                                                lacc[wv][0], lacc[wv][1], pt, par, help, hl);
   stamp_end(tstamp);
 }
 
@@ -3964,6 +4014,7 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
   const float fs0 = st.reuse ? prv.f[gi] : fs, tz0 = st.reuse ? prv.tz[gi] : tz;
   const uint32_t an0 = st.reuse ? prv.ang[gi] : p.an;
   const float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+  const bool pot = d->pot.phi != nullptr;
   const PConst pc = load_pconst(d, si);
   if (mem) {
     sc.bq[gi] = p.qx;
@@ -3991,6 +4042,13 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
   }
   for (int s = 0; s < n_steps; ++s) {
     if (mem) lp[tid] = make_uint2(p.qx, p.qy);
+    float fxs_e = fex, fys_e = fey;  // this sub-step's external force
+    if (pot) {  // (idle threads read member 0's cell: in bounds, never used)
+      float F[3];
+      potential_force<2>(d->pot, p.qx, p.qy, 0u, F);
+      fxs_e = fex + F[0];
+      fys_e = fey + F[1];
+    }
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
@@ -4020,7 +4078,7 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
         wall_forces<2>(d, si, (float)p.qx * sx0, (float)p.qy * sx1, 0.0f, fxs, fys, az,
                        st.wall_viol);
       }
-      bd_step(pc, p, fxs, fys, s == 0 ? fs0 : fs, s == 0 ? tz0 : tz, fex, fey, k0, k1,
+      bd_step(pc, p, fxs, fys, s == 0 ? fs0 : fs, s == 0 ? tz0 : tz, fxs_e, fys_e, k0, k1,
               (uint32_t)i, step0 + (uint64_t)s, s == n_steps - 1, &vx, &vy, &om,
               s == 0 ? an0 : p.an, nullptr, &noise, s == 0);
       const float ddx = (float)(int32_t)(p.qx - q0x) * sx0;
@@ -4226,7 +4284,14 @@ __global__ __launch_bounds__(256) void k_nl_step2(const Derived* __restrict__ d,
   const uint32_t an_swim = reuse0 ? prv.ang[gi] : p.an;
   const PConst pc = load_pconst(d, si);
   float vx = 0.0f, vy = 0.0f, om = 0.0f;
-  bd_step(pc, p, ax, ay, fs, tz, st.f_ext[gi], st.f_ext[M + gi], d->key0, d->key1 ^ (uint32_t)e,
+  float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
+  if (d->pot.phi) {
+    float F[3];
+    potential_force<2>(d->pot, p.qx, p.qy, 0u, F);
+    fex = fex + F[0];
+    fey = fey + F[1];
+  }
+  bd_step(pc, p, ax, ay, fs, tz, fex, fey, d->key0, d->key1 ^ (uint32_t)e,
           (uint32_t)i, step, last, &vx, &vy, &om, an_swim);
   if (last) {  // nobody reads st.q during the window
     st.q[gi] = p.qx;

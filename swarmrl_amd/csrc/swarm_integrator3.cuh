@@ -186,10 +186,17 @@ __device__ void block_global_run3(const Derived* __restrict__ d, const DevState&
       const float vs[3] = {first ? prv.dir3[gi] : v[0], first ? prv.dir3[M + gi] : v[1],
                            first ? prv.dir3[2 * M + gi] : v[2]};
       float f[3], dq[3], ph[3];
+      float fex[3] = {st.f_ext[gi], st.f_ext[M + gi], st.f_ext[2 * M + gi]};
+      if (d->pot.phi) {  // the field at the folded position, every sub-step
+        float F[3];
+        potential_force<3>(d->pot, q[0], q[1], q[2], F);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) fex[a] = fex[a] + F[a];
+      }
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-        f[a] = f[a] + st.f_ext[a * M + gi];
+        f[a] = f[a] + fex[a];
         f[a] = f[a] + fs * vs[a];
       }
       if (sd_mode) {
@@ -542,7 +549,8 @@ __device__ __forceinline__ void pair_fix_sel3(float cut2, float sig6, float eps2
 // turn does not depend on the forces, so it is computed while the force sums
 // are in flight.  Normals are drawn here (translation: StepNoise, the
 // step_normals numbers; rotation: normals3 tag 2).
-template <bool kMulti, bool kWalls>
+// kPot (host-chosen, as kWalls): the engine has a gridded potential.
+template <bool kMulti, bool kWalls, bool kPot = false>
 __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const DevState& st,
                                           const Scratch& sc, int n_envs, int n_steps,
                                           uint64_t step0, int gw, int lane, uint4* lpos_w,
@@ -619,6 +627,15 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
       noise.next(k0, k1, (uint32_t)i, step, kFirst, gt);
       normals3(k0, k1, (uint32_t)i, step, 2u, gr);
     }
+    // the field at this sub-step's (folded) positions: its loads land while
+    // the pair sums are in flight (idle lanes read particle 0's cell)
+    float fxs[3] = {fex[0], fex[1], fex[2]};
+    if constexpr (kPot) {
+      float F[3];
+      potential_force<3>(d->pot, q[0], q[1], q[2], F);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) fxs[a] = fex[a] + F[a];
+    }
     if (kPass > 0) {
       lpos_w[lane] = make_uint4(q[0], q[1], q[2], 0u);
       wave_lds_sync();
@@ -675,7 +692,7 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-      f[a] = f[a] + fex[a];
+      f[a] = f[a] + fxs[a];
       f[a] = f[a] + fs * (kFirst ? vs0[a] : v[a]);
       float dq = f[a] * mob_dt;
       if (noisy) dq = dq + sig_t * gt[a];
@@ -766,7 +783,7 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
 
 // 3-D cluster run: 64 or 256 threads per block (one wave per CU for
 // latency-bound windows, four otherwise), one wave per 64 slots.
-template <bool kMulti, bool kWalls>
+template <bool kMulti, bool kWalls, bool kPot = false>
 __global__ __launch_bounds__(256) void k_cluster_run3(const Derived* __restrict__ d, DevState st,
                                                       Scratch sc, int n_envs, int n_steps,
                                                       const uint64_t* __restrict__ ctl) {
@@ -778,8 +795,8 @@ __global__ __launch_bounds__(256) void k_cluster_run3(const Derived* __restrict_
   const uint64_t step0 = ctl[kCtlStep];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int gw = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-  run_wave3<kMulti, kWalls>(d, st, sc, n_envs, n_steps, step0, gw, lane, lpos[wv], lacc[wv][0],
-                            lacc[wv][1], lacc[wv][2], pt, par);
+  run_wave3<kMulti, kWalls, kPot>(d, st, sc, n_envs, n_steps, step0, gw, lane, lpos[wv],
+                                  lacc[wv][0], lacc[wv][1], lacc[wv][2], pt, par);
 }
 
 // 3-D check, one workgroup per env: k_check's exact validity test of the
@@ -1075,10 +1092,17 @@ __global__ __launch_bounds__(256) void k_nl_step3(const Derived* __restrict__ d,
     step_normals(k0, k1, (uint32_t)i, step, gt);
     normals3(k0, k1, (uint32_t)i, step, 2u, gr);
   }
+  float fex[3] = {st.f_ext[gi], st.f_ext[M + gi], st.f_ext[2 * M + gi]};
+  if (d->pot.phi) {
+    float F[3];
+    potential_force<3>(d->pot, q[0], q[1], q[2], F);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) fex[a] = fex[a] + F[a];
+  }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-    f[a] = f[a] + st.f_ext[a * M + gi];
+    f[a] = f[a] + fex[a];
     f[a] = f[a] + fs * vs[a];
     float dq = f[a] * d->mob_dt[si];
     ph[a] = tq[a] * d->rot_dt[si];

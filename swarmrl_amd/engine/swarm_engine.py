@@ -275,6 +275,8 @@ class SwarmEngine(Engine):
         self._ext_force = {}  # type -> constant force, simulation units (composed at upload)
         self._walls = []  # swarm_wall_t dicts (add_confining_walls / add_walls)
         self._rod = None  # add_rod: first index, particles, bead spacing, fixed, type
+        # add_external_potential: {"phi": fp64 (nx, ny, nz), "h": fp64 (3,)}, simulation units
+        self._potential = None
         self._native: _NativeEngine = None
         self._host_cache = None
         self._view = None
@@ -637,14 +639,19 @@ class SwarmEngine(Engine):
         )
         return center_part
 
-    def _validate_rod(self, rod=None, force_types=None):
+    def _validate_rod(self, rod=None, force_types=None, potential=False):
         """What the rod path cannot run: refused when the rod is added and
-        again at the first integrate (walls or colloids added after it)."""
+        again at the first integrate (walls or colloids added after it).
+        potential: an external potential is about to be added."""
         rod = self._rod if rod is None else rod
         if rod is None:
             return
         if self._walls:
             raise NotImplementedError("a rod together with walls is not implemented")
+        # k_rod_run does not read the field
+        if self._potential is not None or potential:
+            raise NotImplementedError(
+                "a rod together with an external potential is not implemented")
         if not self.params.periodic:
             raise NotImplementedError("a rod in a non-periodic box is not implemented")
         # the rod kernel moves the rod from the colloids' contact forces alone
@@ -742,6 +749,90 @@ class SwarmEngine(Engine):
         self._walls.append(wall)
         self.system.constraints.append(wall)
 
+    def add_lattice_boltzmann(self, agrid: Quantity = None, lb_time_step: Quantity = None,
+                              dynamic_viscosity: Quantity = None, fluid_density: Quantity = None,
+                              boundary_mask: np.array = None, ext_force_density: Quantity = None,
+                              use_GPU: bool = False):
+        """espresso.py:853-938: the reference refuses it with the Brownian
+        thermostat (espresso.py:887-891), the only one this engine runs.  With
+        thermostat_type "langevin", where the reference goes on to build the
+        fluid, this raises NotImplementedError (as the first integrate does
+        for that thermostat)."""
+        if not self.params.thermostat_type == "langevin":
+            raise RuntimeError(
+                "Coupling to lattice boltzmann does not work with a Brownian"
+                " thermostat. Use 'langevin'."
+            )
+        raise NotImplementedError("lattice Boltzmann coupling is not implemented in this build")
+
+    def add_flowfield(self, flowfield: Quantity, friction_coeff: Quantity,
+                      grid_spacings: Quantity):
+        """espresso.py:940-993: refused with the Brownian thermostat as the
+        reference does (espresso.py:967-971).  With thermostat_type
+        "langevin", where the reference adds the FlowField constraint, this
+        raises NotImplementedError."""
+        if not self.params.thermostat_type == "langevin":
+            raise RuntimeError(
+                "Coupling to a flowfield does not work with a Brownian thermostat. Use"
+                " 'langevin'."
+            )
+        raise NotImplementedError("flow field coupling is not implemented in this build")
+
+    def add_external_potential(self, potential: Quantity, grid_spacings: Quantity):
+        """
+        A gridded external potential (espresso.py:995-1036): potential has
+        shape (n_cells_x, n_cells_y, n_cells_z) and units of energy, value
+        [i, j, k] at the cell centre ((i + .5) hx, (j + .5) hy, (k + .5) hz);
+        grid_spacings are the three cell sizes (2-D: one cell along z,
+        grid_spacings[2] = box_l).  The field is periodic and interpolated
+        linearly; every particle feels minus its gradient at the folded
+        position, in every sub-step and in the overlap removal.  The grid has
+        to tile the box.  A second call with the same grid adds to the field
+        (ESPResSo sums its constraints).  Not together with a rod.
+        """
+        pot = np.asarray(potential.m_as("sim_energy"), dtype=float)
+        agrids = np.asarray(grid_spacings.m_as("sim_length"), dtype=float)
+        if not pot.ndim == 3:
+            raise ValueError("potential must have shape (n_cells_x, n_cells_y, n_cells_z)")
+        if not len(grid_spacings) == 3:
+            raise ValueError("Grid spacings must have length of 3")
+        self._check_already_initialised()
+        if pot.size == 0 or not np.all(np.isfinite(pot)):
+            raise ValueError("potential must be non-empty and finite")
+        if not (np.all(np.isfinite(agrids)) and np.all(agrids > 0)):
+            raise ValueError("Grid spacings must be positive")
+        if self.n_dims == 2 and pot.shape[2] != 1:
+            raise ValueError(
+                "a 2d simulation takes a potential with one cell in z"
+                f" (choose grid_spacings[2]=box_l). You gave shape {pot.shape}"
+            )
+        extent = np.asarray(pot.shape, dtype=float) * agrids
+        if np.any(np.abs(extent - self._box) > 1e-9 * self._box):
+            raise ValueError(
+                f"the potential grid must tile the box: {pot.shape} cells of {agrids}"
+                f" span {extent}, the box is {self._box}"
+            )
+        # (the 2-D device copy holds the four corners of every cell)
+        if pot.size * (4 if self.n_dims == 2 else 1) > 2**31 - 1:
+            raise ValueError("the potential grid is too large")
+        self._validate_rod(potential=True)
+        if self._potential is not None:
+            old = self._potential
+            if old["phi"].shape != pot.shape or not np.array_equal(old["h"], agrids):
+                raise NotImplementedError(
+                    "external potentials on different grids are not implemented")
+            old["phi"] = old["phi"] + pot
+            return
+        self._potential = {"phi": pot.copy(), "h": agrids.copy()}
+        self.system.constraints.append(self._potential)
+
+    def _upload_potential(self):
+        phi = np.ascontiguousarray(self._potential["phi"], dtype=np.float32)
+        h = np.ascontiguousarray(self._potential["h"], dtype=np.float64)
+        nx, ny, nz = phi.shape
+        self._native.call("swarm_engine_set_potential_field", phi.ctypes.data, int(nx), int(ny),
+                          int(nz), h.ctypes.data)
+
     def wall_violations(self) -> int:
         """Wall contacts with distance <= 0 so far (ESPResSo raises on those)."""
         if self._native is None:
@@ -824,6 +915,8 @@ class SwarmEngine(Engine):
                 arr[k].offset = float(w.get("offset", 0.0))
             self._native.call("swarm_engine_set_walls", ctypes.cast(arr, ctypes.c_void_p),
                               len(self._walls))
+        if self._potential is not None:  # before the overlap removal: a constraint acts there
+            self._upload_potential()
 
         if self._rod is not None:
             rod = _capi.SwarmRod()
