@@ -18,10 +18,11 @@
 #include <mutex>
 #include <type_traits>
 
+#include "swarm_select.h"
+
 namespace {
 
-template <int V>
-using Int = std::integral_constant<int, V>;
+using swarm_select::Int;
 
 // ---- argument checks (null: within the limits)
 

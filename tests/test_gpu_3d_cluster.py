@@ -104,6 +104,34 @@ def test_cluster3_4096_bit_exact(E, n_species, path3):
         step += nsteps
 
 
+def test_cluster3_above_4096_colloids_bit_exact(monkeypatch):
+    """One env of 4913 colloids (17^3): above 4096 the 3-D build sort takes 16
+    colloids per thread (k_build_sort3<16>).  Two cluster windows of 5
+    sub-steps, no re-run, bit-exact."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_NLIST", "0")
+    rng = np.random.default_rng(43)
+    n = 17 ** 3
+    pos, d, L = _lattice3(rng, n)
+    box = [L, L, L]
+    sp = np.zeros(n, int)
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 19, species_list()[:1], sp, n_dims=3)
+    st = oracle.state3_from_positions(pos, d, box)
+    h.upload([st])
+    for w in range(2):
+        f = rng.choice([0.0, 10.0], n).astype(np.float32)
+        tq = rng.normal(scale=5.0, size=(3, n)).astype(np.float32)
+        h.set_actions(f, tq[2])
+        h.set_torque_xy(tq[:2])
+        h.integrate(5)
+        fb, waves = _stats(h)
+        assert fb[0] == 0 and waves[0] > 0, (w, fb, waves)
+        st, v, om = oracle.bd_run3(h.op, st, sp, f, tq, 5, step0=5 * w)
+        _eq3(h.download()[0], st)
+        assert np.array_equal(h.velocities(), v) and np.array_equal(h.omegas3(), om)
+
+
 def test_cluster3_matches_global_path(monkeypatch):
     """The same engine run on the three 3-D paths (SWARMRL_AMD_CLUSTER_PATH=0
     forces the global one) gives the same bits."""

@@ -192,6 +192,61 @@ def test_slab_walls_cluster_path_bit_exact():
     assert h.wall_violations() == 0
 
 
+def test_confining_walls_throughput_run_bit_exact(monkeypatch):
+    """k_cluster_run<false, false, true, false>: the walls as its only variant
+    flag (one species, no potential; SWARMRL_AMD_WIDE_RUN=0 for the
+    throughput kernel and SWARMRL_AMD_NOISE_TABLE=0 for normals drawn in the
+    kernel, which so small an engine would otherwise read from the table):
+    two envs of 64 swimmers heading for x = L inside box-face walls, some of
+    them in reach of it from the start, three windows on cluster waves
+    without a re-run (0.21 um of drift a window, well below half the skin),
+    bit-identical to the oracle, whose run without the walls differs."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_WIDE_RUN", "0")
+    monkeypatch.setenv("SWARMRL_AMD_NOISE_TABLE", "0")
+    rng = np.random.default_rng(47)
+    E, k, a = 2, 8, 6.0
+    n, L = k * k, k * a
+    box = [L, L, L]
+    walls = [{"kind": 0, "normal": [1, 0, 0], "offset": 0.0},
+             {"kind": 0, "normal": [-1, 0, 0], "offset": -L},
+             {"kind": 0, "normal": [0, 1, 0], "offset": 0.0},
+             {"kind": 0, "normal": [0, -1, 0], "offset": -L}]
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 6, species_list()[:1], np.zeros(n, int), n_envs=E)
+    # a jittered lattice shifted towards x = L and y = L: its last column and
+    # row start within reach of those walls
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 2)
+    states = []
+    for _ in range(E):
+        pos = np.zeros((n, 3))
+        pos[:, :2] = 1.2 + (g + 0.5) * a + rng.uniform(-1.0, 1.0, (n, 2))
+        dirs = np.tile([1.0, 0.0, 0.0], (n, 1))
+        states.append(oracle.state_from_positions(pos, dirs, box))
+    h.upload(states)
+    h.set_walls(walls)
+    h.sd(100)
+    refs = [oracle.sd_run(h.op, st, np.zeros(n), 100, walls=walls)[0] for st in states]
+    free = refs[0]
+    f = np.full(E * n, 10.0, np.float32)
+    h.set_actions(f, np.zeros(E * n, np.float32))
+    for w in range(3):
+        h.integrate(100)
+        got = h.download()
+        for e in range(E):
+            refs[e], _, _ = oracle.bd_run(h.op, refs[e], np.zeros(n), f[:n], np.zeros(n), 100,
+                                          step0=100 * w, env=e, walls=walls)
+            for k in ("q", "img", "ang"):
+                assert np.array_equal(got[e][k], refs[e][k]), (w, e, k)
+        free, _, _ = oracle.bd_run(h.op, free, np.zeros(n), f[:n], np.zeros(n), 100, step0=100 * w)
+        fb, waves = h.window_stats()
+        assert np.all(fb == 0) and np.all(waves > 0), (w, fb, waves)
+    assert not np.array_equal(free["q"], refs[0]["q"])  # the walls were felt
+    pos = oracle.unwrapped(got[0], box, 2)
+    assert np.all(pos[:, :2] > 0.0) and np.all(pos[:, :2] < L)
+    assert h.wall_violations() == 0
+
+
 def test_wall_violation_is_counted():
     from gpu_harness import Harness, species_list
 

@@ -434,3 +434,125 @@ def test_a_captured_run_alone_keeps_its_check(monkeypatch):
         assert np.array_equal(got["1"][0][k], got["0"][0][k]), k
     assert got["1"][1][3] == got["0"][1][3], (got["1"][1], got["0"][1])  # windows checked
     assert sum(got["1"][2]) == 0, got["1"][2]
+
+
+# ------------------------------------------- above 4096 colloids per env
+def _lattice_state(seed, k=65, a=5.0):
+    """k x k colloids (4225: the one-workgroup sorts take 16 colloids per
+    thread above 4096) on a square lattice of spacing a, jittered by 1 um: no
+    overlaps, no cluster wider than a wave."""
+    rng = np.random.default_rng(seed)
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 2)
+    pos = np.zeros((k * k, 3))
+    pos[:, :2] = (g + 0.5) * a + rng.uniform(-1.0, 1.0, (k * k, 2))
+    th = 2 * np.pi * rng.random(k * k)
+    box = [k * a, k * a, k * a]
+    dirs = np.stack([np.cos(th), np.sin(th), np.zeros(k * k)], 1)
+    return rng, box, oracle.state_from_positions(pos, dirs, box)
+
+
+def _actions(rng, n):
+    return (rng.choice([0.0, 10.0], n).astype(np.float32),
+            rng.choice([-10.0, 0.0, 10.0], n).astype(np.float32))
+
+
+@pytest.mark.parametrize("switch", ["0", "1"])
+def test_reward_launch_above_4096_colloids_matches_oracle(switch, monkeypatch):
+    """One env of 4225 colloids with the plain pair search (SWARMRL_AMD_LOCAL_UF=0,
+    so the slice's launches carry the build and the pair search): the reward
+    launch carries the 16-per-thread build sort and, with the switch on, the
+    window's check (k_field_vgrid_sort<16, kCheck>).  Two windows of 5
+    sub-steps; states, rewards and the field history bit-exact against the
+    oracle."""
+    rng, box, st0 = _lattice_state(31)
+    n = len(st0["ang"])
+    monkeypatch.setenv("SWARMRL_AMD_LOCAL_UF", "0")
+    s = _Seq(switch, box, [st0], 13, monkeypatch)
+    acts = [_actions(rng, n) for _ in range(2)]
+    for f, t in acts:
+        s.h.set_actions(f, t)
+        s.window(5)
+    got = s.result()
+    print("check_stats", got["check_stats"], "build_stats", got["build_stats"])
+    assert sum(got["check_stats"]) == (2 if switch == "1" else 0), got["check_stats"]
+    agents = np.arange(n)
+    src = np.array([box[0] / 2, box[1] / 2, 0.0])
+    hist = {"q": np.zeros((3, n), np.uint32), "img": np.zeros((3, n), np.int32)}
+    st = st0
+    for w, (f, t) in enumerate(acts):
+        st, _, _ = oracle.bd_run(s.h.op, st, np.zeros(n), f, t, 5, step0=5 * w)
+        dc, dp = oracle.field_distance(s.h.op, st, agents, src, np.array(box), hist, update=True)
+        dcur, dprev, hq, himg = got["rewards"][w]
+        assert np.array_equal(dcur, dc) and np.array_equal(dprev, dp), w
+        assert np.array_equal(hq.view(np.uint32), hist["q"]), w
+        assert np.array_equal(himg, hist["img"]), w
+    assert not np.array_equal(got["rewards"][1][0], got["rewards"][1][1])  # the colloids moved
+    for k in ("q", "img", "ang"):
+        assert np.array_equal(got["state"][0][k], st[k]), k
+
+
+@pytest.mark.parametrize("k,local_uf", [(65, "0"), (65, "1"), (6, "0")])
+def test_deferred_build_carried_by_the_cone_or_flushed_matches_oracle(k, local_uf, monkeypatch):
+    """The deferred build carried by the vision cone and with no carrier at
+    all (its three stages flushed before the window: k_build_sort<CH>,
+    k_build_pairs<kLocal>, k_cluster_build<false, kLocal>); cone and states
+    bit-exact against the oracle.  4225 colloids (k = 65): k_vgrid_sort<16>,
+    then with the block-local pair search k_vision_pairs<.., true>, with the
+    plain one the pair search beside the sort.  36 colloids in a 30 um box
+    (k = 6: four build cells a side, too few for the candidate lists):
+    k_vgrid_sort<4>, then k_vision_pairs<.., false>."""
+    from gpu_harness import Harness, species_list
+    from swarmrl_amd.engine import ops
+
+    rng, box, st = _lattice_state(32, k=k)
+    n = len(st["ang"])
+    monkeypatch.setenv("SWARMRL_AMD_LOCAL_UF", local_uf)
+    monkeypatch.setenv("SWARMRL_AMD_NLIST", "0")
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 14, species_list()[:1], np.zeros(n, int))
+    h.upload([st])
+    agents = np.arange(0, n, 4, dtype=np.int32)
+    radii = np.ones(n, np.float32)
+    types = np.zeros(n, np.int32)
+    t_agents = torch.as_tensor(agents, device=dev)
+    t_radii = torch.as_tensor(radii, device=dev)
+    t_types = torch.as_tensor(types, device=dev)
+    vp = ops.vision_params(10.0, np.pi / 2, 3, [0])
+
+    def defer():
+        deferred = ctypes.c_int32()
+        h.native.bind_stream()
+        h.native.call("swarm_engine_defer_build", ctypes.byref(deferred))
+        assert deferred.value == 1
+
+    step = 0
+    for carrier in (True, False, True):
+        f, t = _actions(rng, n)
+        h.set_actions(f, t)
+        h.integrate(5)
+        st, _, _ = oracle.bd_run(h.op, st, np.zeros(n), f, t, 5, step0=step)
+        step += 5
+        defer()
+        if carrier:
+            out = ops.vision_cone(h.native, 1, t_agents, t_radii, t_types, vp).cpu().numpy()
+            ref = oracle.vision_cone(h.op, st, agents, radii, types, 10.0, np.pi / 2, 3, [0],
+                                     cells=True)
+            assert np.array_equal(out[0], ref)
+            assert np.count_nonzero(ref) > len(agents)
+    f, t = _actions(rng, n)
+    h.set_actions(f, t)
+    h.integrate(5)
+    st, _, _ = oracle.bd_run(h.op, st, np.zeros(n), f, t, 5, step0=step)
+    got = h.download()[0]
+    for key in ("q", "img", "ang"):
+        assert np.array_equal(got[key], st[key]), key
+    fb, waves = h.window_stats()
+    assert fb[0] == 0 and waves[0] > 0, (fb, waves)
+    # what the host can see of the carrier: with the candidate lists (4225
+    # colloids, plain pair search) the pair search of both carried builds ran
+    # as a role of the cone's grid launch and counted itself
+    filtered, waited, _, _ = _stats(h.native, "swarm_engine_build_stats")
+    print("build_stats", filtered, waited)
+    if k == 65 and local_uf == "0":
+        assert filtered + waited >= 2, (filtered, waited)

@@ -128,6 +128,68 @@ def test_l1_pairs_and_fused_policy_match_oracle(force):
         assert max(moved) > 1.5 and waited > 0, (moved, list(stats))
 
 
+def test_fused_policy_at_four_lanes_per_agent_matches_oracle(monkeypatch):
+    """SWARMRL_AMD_VISION_G=4: no build stage rides in a cone of that width, so
+    the fused cone + policy launch is k_vision_policy<4, 4, 4, 4> (the deferred
+    build is flushed ahead of it).  1024 colloids, one eager slice and the
+    three of the episode's capture: features, log-probabilities, rewards and
+    the final state against the oracle's replay of the recorded actions."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setenv("SWARMRL_AMD_VISION_G", "4")
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    N = 1024
+    ns = argparse.Namespace(colloids=N, envs_per_gpu=1, write_interval=1.0)
+    eng, ff, agent = bench.build_workload(ns, 42, dev)
+    pos0 = np.stack(eng._pos[0])
+    dir0 = np.stack(eng._dir[0])
+    eng.integrate(1, ff)
+    _, episode_graph, warm = bench.capture_episode(eng, ff, agent, 3)
+    block = _host(warm)
+    torch.cuda.synchronize()
+    eng.drain_trajectory(block=True)
+    got = eng.get_raw_state()
+    del episode_graph
+
+    L = float(eng._box[0])
+    box = np.array([L, L, L])
+    src = np.array([L / 2, L / 2, 0.0])
+    p = oracle.make_params(eng._box, eng._time_step, eng._kT(),
+                           eng.params.WCA_epsilon.m_as("sim_energy"), 42, [eng._species_keys[0]])
+    agents = np.arange(N)
+    radii = np.ones(N, np.float32)
+    types = np.zeros(N, np.int32)
+    ftab = np.array([0.0, 10.0, 0.0, 0.0], np.float32)
+    ttab = np.array([10.0, 0.0, -10.0, 0.0], np.float32)
+    sp = np.zeros(N, np.uint8)
+    st = oracle.state_from_positions(pos0, dir0, eng._box)
+    hist = oracle.history_from_state(st, agents)
+    st, _ = oracle.sd_run(p, st, sp, 1000)
+    prev = {"f": np.zeros(N, np.float32), "t": np.zeros(N, np.float32), "ang": st["ang"].copy()}
+    n_slices = len(block["actions"])
+    assert n_slices == 3
+    for s in range(n_slices):
+        obs = oracle.vision_cone(p, st, agents, radii, types, 10.0, np.pi / 2, 3, [0], cells=True)
+        assert np.array_equal(block["features"][s].reshape(obs.shape), obs), (s, "cone")
+        with torch.no_grad():
+            x = torch.as_tensor(obs.reshape(N, 3), device=dev)
+            w1, b1, w2, b2 = agent.network.model.rollout_layers()
+            lg = torch.relu(x @ w1.T + b1) @ w2.T + b2
+            ref = torch.log(torch.softmax(lg, -1) + 1e-8)
+        idx = block["actions"][s].reshape(-1)
+        want = ref.gather(1, torch.as_tensor(idx, device=dev).view(-1, 1)).view(-1).cpu().numpy()
+        np.testing.assert_allclose(block["log_probs"][s].reshape(-1), want, rtol=0, atol=2e-5)
+        f, t = ftab[idx], ttab[idx]
+        st, _, _ = oracle.bd_run(p, st, sp, f, t, 100, step0=100 * s, prev=prev)
+        prev = {"f": f, "t": t, "ang": st["ang"].copy()}
+        rew = _reward(p, st, agents, src, box, hist)
+        assert np.array_equal(block["rewards"][s].reshape(-1), rew), (s, "reward")
+    for k in ("q", "img", "ang"):
+        assert np.array_equal(got[k], st[k]), k
+
+
 def test_field_observable_rides_the_build_and_matches_oracle():
     """The same schedule with a concentration-field observable (BASELINE C3's
     find-centre workload, bench.build_c3_workload): the deferred build rides

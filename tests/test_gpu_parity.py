@@ -411,6 +411,39 @@ def test_c5_16384_large_build_bit_exact():
     assert fb[0] == 0 and w[0] > 0, (fb, w)
 
 
+@pytest.mark.parametrize("k", [92, 145])
+def test_large_build_plain_pair_search_bit_exact(k, monkeypatch):
+    """The one-workgroup large-N cluster builds, which the plain pair search
+    (SWARMRL_AMD_LOCAL_UF=0) leaves to a 2-D env: k_cluster_build_packed
+    (8464 colloids: the LDS build's 5 words per colloid no longer fit, the
+    packed build's 2 do) and k_cluster_build<true, false> (21 025: the forest
+    alone in LDS).  One env on a jittered lattice, two windows of 5 sub-steps
+    on cluster waves, bit-exact."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_LOCAL_UF", "0")
+    monkeypatch.setenv("SWARMRL_AMD_NLIST", "0")
+    rng = np.random.default_rng(90 + k)
+    n, a = k * k, 5.0
+    box = [k * a, k * a, k * a]
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 2)
+    pos = np.zeros((n, 3))
+    pos[:, :2] = (g + 0.5) * a + rng.uniform(-1.0, 1.0, (n, 2))
+    th = 2 * np.pi * rng.random(n)
+    st = oracle.state_from_positions(pos, np.stack([np.cos(th), np.sin(th), np.zeros(n)], 1), box)
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 3, species_list()[:1], np.zeros(n, int))
+    h.upload([st])
+    for w in range(2):
+        f = rng.choice([0.0, 10.0], n).astype(np.float32)
+        t = rng.choice([-10.0, 0.0, 10.0], n).astype(np.float32)
+        h.set_actions(f, t)
+        h.integrate(5)
+        st, _, _ = oracle.bd_run(h.op, st, np.zeros(n), f, t, 5, step0=5 * w)
+        _eq(h.download()[0], st)
+        fb, waves = h.window_stats()
+        assert fb[0] == 0 and waves[0] > 0, (w, fb, waves)
+
+
 @pytest.mark.parametrize("E,n,box_len,env", [
     (1, 2000, 90.0, {}),                                   # 16 lanes per agent
     (20, 4096, 200.0, {"SWARMRL_AMD_VISION_G": "4"}),
@@ -447,6 +480,41 @@ def test_vision_cone_parity_lane_variants_and_dense(E, n, box_len, env, monkeypa
         ref = oracle.vision_cone(h.op, states[e], agents, radii, types, 12.0, 1.0, 3, [0, 1])
         assert np.array_equal(out[e], ref)
         assert np.count_nonzero(ref) > len(agents)
+
+
+@pytest.mark.parametrize("lanes", ["4", "16"])
+@pytest.mark.parametrize("n_cones,detected", [(3, [1]), (5, [0, 1, 2]), (9, [0, 1]), (16, [0, 1])])
+def test_vision_cone_parity_every_bin_width_at_both_lane_counts(n_cones, detected, lanes,
+                                                                monkeypatch):
+    """k_vision<NB, G> for each bin width (n_cones * n_types = 3, 15, 18 and 32
+    bins: NB = 4, 16, 32, 32 at its limit) at 4 and 16 lanes per agent, two
+    envs of 100 colloids, bit-exact against the oracle.  (NB = 8 at both lane
+    counts: test_vision_cone_parity_lane_variants_and_dense.)"""
+    from gpu_harness import Harness, random_state, species_list
+    from swarmrl_amd.engine import ops
+
+    monkeypatch.setenv("SWARMRL_AMD_VISION_G", lanes)
+    rng = np.random.default_rng(70 + n_cones)
+    box = [40.0, 40.0, 40.0]
+    n, E = 100, 2
+    types = rng.integers(0, 3, n)
+    h = Harness(box, 1e-3, 0.0, 1.0, 0, species_list(), np.zeros(n, int), n_envs=E)
+    states = [random_state(rng, n, box) for _ in range(E)]
+    h.upload(states)
+    agents = np.nonzero(types == 1)[0].astype(np.int32)
+    radii = (0.5 + rng.random(n)).astype(np.float32)
+    dev = torch.device("cuda", 0)
+    vp = ops.vision_params(12.0, 1.3, n_cones, detected)
+    out = ops.vision_cone(h.native, E, torch.as_tensor(agents, device=dev),
+                          torch.as_tensor(radii, device=dev),
+                          torch.as_tensor(types.astype(np.int32), device=dev), vp)
+    out = out.cpu().numpy()
+    for e in range(E):
+        ref = oracle.vision_cone(h.op, states[e], agents, radii, types, 12.0, 1.3, n_cones,
+                                 detected)
+        assert np.array_equal(out[e], ref)
+        # hits in most bins, so a bin summed into a neighbour's slot would show
+        assert np.count_nonzero(ref.reshape(len(agents), -1).sum(0)) >= 0.75 * n_cones * len(detected)
 
 
 @pytest.mark.parametrize("wide", ["1", "0"])

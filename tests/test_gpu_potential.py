@@ -224,6 +224,91 @@ def test_run_wave_potential_bit_exact(wide, table, monkeypatch):
     assert frac >= 0.1
 
 
+def test_run_wave_potential_alone_throughput_bit_exact(monkeypatch):
+    """k_cluster_run<false, false, false, true>: the potential as its only
+    variant flag (one species, no walls; SWARMRL_AMD_WIDE_RUN=0 for the
+    throughput kernel and SWARMRL_AMD_NOISE_TABLE=0 for normals drawn in the
+    kernel, which so small an engine would otherwise read from the table): 2
+    envs of 64 colloids on a jittered lattice, chunks of 20, 1 and 40
+    sub-steps on cluster waves without fallback."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_WIDE_RUN", "0")
+    monkeypatch.setenv("SWARMRL_AMD_NOISE_TABLE", "0")
+    rng = np.random.default_rng(221)
+    E, k, a = 2, 8, 6.0
+    n, L = k * k, k * a
+    box = [L, L, L]
+    shape = (13, 11, 1)
+    sp = np.zeros(n, int)
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 42, species_list()[:1], sp, n_envs=E)
+    states = []
+    for _ in range(E):
+        pos, dirs = _lattice(rng, k, a, 0.0, 1.0)
+        states.append(oracle.state_from_positions(pos, dirs, box))
+    h.upload(states)
+    phi, spacing, inv_h = _field(rng, shape, box, 4.0)
+    f_ext = _forces(rng, E, n, 0.5, xy_max=1.0)
+    h.set_external_force(f_ext)
+    _set_potential(h, phi, spacing)
+
+    def actions(m):
+        return (rng.uniform(1.0, 4.5, m).astype(np.float32),
+                rng.normal(size=m).astype(np.float32) * 5)
+
+    _run_chunks_2d(h, states, sp, f_ext, phi, inv_h, (20, 1, 40), actions,
+                   expect=lambda fb, w: np.all(fb == 0) and np.all(w > 0),
+                   tag="run_wave potential alone")
+
+
+def test_run_wave3_potential_alone_bit_exact(monkeypatch):
+    """k_cluster_run3 with the potential as its only variant flag (one
+    species, no walls): 2 envs of 120 colloids on a jittered cubic lattice,
+    chunks of 20 and 1 sub-steps on cluster waves without fallback."""
+    from gpu_harness import Harness, species_list
+    from test_gpu_3d_cluster import _lattice3
+
+    monkeypatch.setenv("SWARMRL_AMD_CLUSTER_PATH", "1")
+    monkeypatch.setenv("SWARMRL_AMD_NLIST", "0")
+    rng = np.random.default_rng(222)
+    E, n = 2, 120
+    shape = (7, 5, 3)
+    lat = [_lattice3(rng, n, a=6.0) for _ in range(E)]
+    L = lat[0][2]
+    box = [L, L, L]
+    sp = np.zeros(n, int)
+    states = [oracle.state3_from_positions(p, d, box) for p, d, _ in lat]
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 17, species_list()[:1], sp, n_envs=E, n_dims=3)
+    h.upload(states)
+    phi, spacing, inv_h = _field(rng, shape, box, 4.0, dims=3)
+    f_ext = _forces(rng, E, n, 0.5)
+    h.set_external_force(f_ext)
+    _set_potential(h, phi, spacing)
+    plain = states[0]
+    step = 0
+    for nsteps in (20, 1):
+        f = rng.uniform(1.0, 4.5, E * n).astype(np.float32)
+        tq = rng.normal(scale=5.0, size=(3, E * n)).astype(np.float32)
+        h.set_torque_xy(tq[:2])
+        h.set_actions(f, tq[2])
+        h.integrate(nsteps)
+        vels = []
+        for e in range(E):
+            s = slice(e * n, (e + 1) * n)
+            states[e], v, _ = pr.bd_run3_potential(
+                h.op, states[e], sp, f[s], tq[:, s], nsteps, phi, inv_h, step0=step, env=e,
+                f_ext=_fe(f_ext, e))
+            vels.append(v)
+        plain, _, _ = oracle.bd_run3(h.op, plain, sp, f[:n], tq[:, :n], nsteps, step0=step,
+                                     f_ext=_fe(f_ext, 0))
+        step += nsteps
+        _compare(h, states, vels, KEYS3)
+        fb, waves = h.window_stats()
+        print("3-D potential alone window", nsteps, "fallback", fb, "waves", waves)
+        assert np.all(fb == 0) and np.all(waves > 0), (fb, waves)
+    assert not np.array_equal(plain["q"], states[0]["q"])  # the oracle without the potential
+
+
 # ----------------------------------- 2. run_big_clusters, 3. the exact re-run
 def _patch_box(rng, n_free, shape):
     """One 10 x 10 patch at 2.5 um spacing (a cluster wider than a wave) and
