@@ -10,6 +10,9 @@
 //                   k_global also runs steepest descent (espresso.py:1161-1168).
 //   observables     swarm_observe.cuh: k_grid_build, k_vision*, k_field*,
 //                   k_pairs, the trajectory ring.
+//   planning        swarm_plan.h over swarm_sizes.h (plain C++17): the checks,
+//                   cell grids, path choices and buffer sizes an engine fixes
+//                   at creation, one pure function (swarm::plan_engine).
 //   launches        swarm_engine_host.cuh (engine, observables) and
 //                   swarm_learn_host.cuh (policies, PPO); this file keeps the
 //                   engine's state and the C ABI's checks around them.
@@ -40,17 +43,13 @@
 #include "swarm_rnd.cuh"
 #include "swarm_rod.cuh"
 #include "swarm_observe.cuh"
+#include "swarm_plan.h"
 
 namespace {
 
 constexpr double kTwo32 = 4294967296.0;
 constexpr double kTwoPi = 6.283185307179586476925;
-// Verlet skin of the cluster decomposition (um): pairs closer than
-// r_i + r_j + skin at the window start share a cluster.  Performance only:
-// results do not depend on it.  2 um keeps inter-cluster approaches below
-// the cutoff over a 100-step slice a ~5-sigma event at the reference's
-// defaults.
-double skin_um() { return 2.0; }
+using swarm::kSkinUm;  // the Verlet skin (swarm_plan.h)
 
 thread_local std::string g_err;
 
@@ -84,21 +83,20 @@ void derive(const swarm_params_t& p, Derived& d) {
     d.sig_v[s] = p.mass[s] > 0.0 ? (float)std::sqrt(kT / p.mass[s]) : 0.0f;
     d.sig_w[s] = p.rinertia[s] > 0.0 ? (float)std::sqrt(kT / p.rinertia[s]) : 0.0f;
   }
-  d.rc_max = 0.0;
+  d.rc_max = swarm::max_cutoff(p);
   for (int s = 0; s < p.n_species; ++s)
     for (int t = 0; t < p.n_species; ++t) {
       const double rc = p.radius[s] + p.radius[t];
       const double rc2 = rc * rc;
       d.cut2[s * kMaxSpecies + t] = (float)rc2;
       d.sig6[s * kMaxSpecies + t] = (float)(rc2 * rc2 * rc2 * 0.5);
-      d.rc_max = std::max(d.rc_max, rc);
     }
   for (int s = 0; s < p.n_species; ++s)
     for (int t = 0; t < p.n_species; ++t) {
-      const double r = p.radius[s] + p.radius[t] + skin_um();
+      const double r = p.radius[s] + p.radius[t] + kSkinUm;
       d.nb2[s * kMaxSpecies + t] = (float)(r * r);
     }
-  d.skin = (float)skin_um();
+  d.skin = (float)kSkinUm;
   d.rc_max_f = (float)d.rc_max;
   d.eps24 = (float)(24.0 * p.wca_epsilon);
   d.n_species = p.n_species;
@@ -113,99 +111,51 @@ void derive(const swarm_params_t& p, Derived& d) {
   }
 }
 
-int ilog2_floor(double v) {
-  int l = 0;
-  while ((double)(1 << (l + 1)) <= v && l < 20) ++l;
-  return l;
-}
-
-// Power-of-two cell grid with side >= cutoff and at most max(n, 64) cells
-// (identical rule in oracle/swarm_oracle.c:or_cell_grid).
-void cell_grid(const swarm_params_t& p, int n, double cutoff, int* lx, int* ly) {
-  int l[2];
-  for (int a = 0; a < 2; ++a) {
-    const double m = cutoff > 0.0 ? p.box[a] / cutoff : 1024.0;
-    l[a] = m >= 1.0 ? ilog2_floor(m) : 0;
-    if (l[a] > 15) l[a] = 15;
-  }
-  const int cap = n > 64 ? n : 64;
-  while ((1 << (l[0] + l[1])) > cap) {
-    if (l[0] >= l[1] && l[0] > 0)
-      l[0]--;
-    else if (l[1] > 0)
-      l[1]--;
-    else
-      break;
-  }
-  *lx = l[0];
-  *ly = l[1];
-}
-
-// 3-D: the same rule over three axes (3-D global path).
-void cell_grid3(const swarm_params_t& p, int n, double cutoff, int* lx, int* ly, int* lz) {
-  int l[3];
-  for (int a = 0; a < 3; ++a) {
-    const double m = cutoff > 0.0 ? p.box[a] / cutoff : 1024.0;
-    l[a] = m >= 1.0 ? ilog2_floor(m) : 0;
-    if (l[a] > 10) l[a] = 10;
-  }
-  const int cap = std::min(n > 64 ? n : 64, 8192);  // counts fit the default 64 KB of LDS
-  while ((1 << (l[0] + l[1] + l[2])) > cap) {
-    int k = 0;
-    for (int a = 1; a < 3; ++a)
-      if (l[a] > l[k]) k = a;
-    if (l[k] == 0) break;
-    l[k]--;
-  }
-  *lx = l[0];
-  *ly = l[1];
-  *lz = l[2];
-}
+using swarm::cell_grid;  // swarm_plan.h (the observables' grids use the same rule)
 
 }  // namespace
 
 // =================================================================== C ABI
-// SWARMRL_AMD_DEFER_CHECK unset: the check of an eligible engine rides in
-// the reward launch (+4 % on the headline)
-constexpr bool kDeferCheckDefault = true;
-
 struct swarm_engine {
+  // ---- fixed at creation
   swarm_params_t params;
   Derived derived;
   int32_t n_envs = 0, n = 0;
-  hipStream_t stream = nullptr;
   int device = 0;
+  int n_cus = 0;
+  // the cell grids, every path choice and the buffer sizes (swarm_plan.h).
+  // Nothing writes it after swarm_engine_create but swarm_engine_set_rod,
+  // which takes the engine off the cluster path for good.
+  swarm::EnginePlan plan;
   DevState st{};
   Scratch sc{};
+  VisionSorted vs{};
   Derived* d_derived = nullptr;
   double* d_box = nullptr;
   uint64_t* d_step = nullptr;
   uint32_t* d_arrive = nullptr;
+  int32_t* d_order = nullptr;  // observable grid scratch (with d_start below)
+  int32_t* d_count = nullptr;
+  float* d_noise = nullptr;  // plan.noise_table: the two noise tables (k_noise)
+  float* own_f_swim = nullptr;
+  float* own_torque_z = nullptr;
+  // every device buffer the engine owns, the lazily created ones below
+  // included (dev_malloc / dev_free); swarm_engine_destroy frees what is listed
+  std::vector<void*> allocs;
+
+  // ---- what a call can change
+  hipStream_t stream = nullptr;
   // trajectory ring (swarm_engine_traj_ring): host-pinned, device-mapped
   unsigned char* traj_host = nullptr;
   unsigned char* traj_dev = nullptr;
   uint64_t* d_traj_count = nullptr;
   int traj_cap = 0, traj_env = 0;
   size_t traj_entry = 0;
-  // observable grid scratch
+  // observable grid scratch, grown on demand
   int32_t* d_start = nullptr;
   size_t start_cap = 0;
-  int32_t* d_order = nullptr;
-  int32_t* d_count = nullptr;
   int32_t* d_pairs = nullptr;
   size_t pairs_cap = 0;
-  int lxg = 0, lyg = 0, lzg = 0;  // global-path grid: cell side >= rc_max (lzg: 3-D)
-  int lxb = 0, lyb = 0, lzb = 0;  // cluster-build grid: cell side >= rc_max + skin
-  bool cluster_path = false;
-  // 3-D boxes whose rc + skin graph percolates: chip-wide sub-steps over a
-  // per-window Verlet list instead of per-wave clusters (swarm_integrator3.cuh)
-  bool nlist_path = false;
-  bool big_build = false;  // k_cluster_build<true>: cluster arrays in global memory
-  bool chip_sort = false;  // 2-D envs above 4096 colloids: the three-launch chip-wide sort
-  VisionSorted vs{};
-  // latency-bound windows read their normals from a table (k_noise)
-  bool noise_table = false;
-  float* d_noise = nullptr;
   // swarm_engine_prebuild: the next window's build (and noise table) were
   // launched ahead on another stream from the current positions
   bool prebuilt = false;
@@ -213,17 +163,15 @@ struct swarm_engine {
   // build (1 sort, 2 pairs, 3 cluster build; 0 none) that rides along in the
   // next observable / policy launch; flushed before a window runs
   int ride_stage = 0;
-  // SWARMRL_AMD_DEFER_CHECK on an eligible engine (l1_pairs): after
+  // plan.defer_check (SWARMRL_AMD_DEFER_CHECK on an l1_pairs engine): after
   // swarm_engine_hint_defer_check the next integrate call leaves its last
   // window's check pending (check_pending, check_steps: its sub-steps)
   // instead of launching k_check; the reward launch that follows carries it
   // (launch_field), anything else flushes it first (flush_check).  Host-side
   // state: it must not outlive a stream capture (swarm_engine_flush_check).
-  bool defer_check = false;
   bool defer_hint = false;
   bool check_pending = false;
   int check_steps = 0;
-  int n_cus = 0;
   // speculative vision grid (swarm_vision_cone_persistent): the last
   // persistent call's arguments; vgrid_ready: the reward launch built the
   // grid of the current positions for them (honoured while the deferred
@@ -234,18 +182,9 @@ struct swarm_engine {
   // swarm_engine_prebuild_noise: the next window's noise table for this many
   // sub-steps was launched ahead (on a stream of the caller's)
   int prebuilt_noise_steps = 0;
-  // Latency-bound engines run k_cluster_run_wide: one block per CU, and
-  // (noise_blocks > 0) the next window's noise table filled beside the run;
-  // next_table_ready: the last window did that (the table's first step and
-  // length are checked on the device, this flag only skips k_noise).
-  bool wide_run = false;
-  int run_wpb = 4;  // run waves per block (= per CU) of k_cluster_run_wide
-  // a rotation helper wave beside each run wave of k_cluster_run_wide
-  // (swarm::rot_helper; run_wpb <= 2)
-  bool rot_helper = true;
-  // k_build_env: the whole build in one LDS-resident workgroup per env
-  bool env_build = false;
-  int noise_blocks = 0;
+  // plan.noise_blocks > 0: the last k_cluster_run_wide filled the next
+  // window's noise table beside the run (the table's first step and length
+  // are checked on the device, this flag only skips k_noise)
   bool next_table_ready = false;
   // swarm_engine_profile: HIP events around every k_cluster_run launch;
   // launches captured into a graph get event-record nodes whose events are
@@ -264,8 +203,6 @@ struct swarm_engine {
   // the k-th captured run node (its k_check, then the next window's build and
   // observable launches), swarm::role_begin / role_end
   unsigned long long* d_rstamp = nullptr;
-  float* own_f_swim = nullptr;
-  float* own_torque_z = nullptr;
   // swarm_engine_set_rod: every sub-step runs on k_rod_run (swarm_rod.cuh)
   bool has_rod = false;
   swarm::RodArgs rod{};
@@ -273,9 +210,33 @@ struct swarm_engine {
   // points at it while a field is set) and its capacity in values
   float* d_pot = nullptr;
   size_t pot_cap = 0;
-  void* allocs[96] = {};
-  int n_allocs = 0;
 };
+
+// Device buffers of the engine: listed in e->allocs before anything else can
+// fail, so that swarm_engine_destroy frees them whatever becomes of the call.
+namespace {
+
+template <typename T>
+hipError_t dev_malloc(swarm_engine* e, T** p, size_t bytes) {
+  void* v = nullptr;
+  const hipError_t err = hipMalloc(&v, bytes);
+  if (err != hipSuccess) return err;
+  e->allocs.push_back(v);
+  *p = reinterpret_cast<T*>(v);
+  return hipSuccess;
+}
+
+// Frees *p (null: nothing to do) and clears it.
+template <typename T>
+hipError_t dev_free(swarm_engine* e, T** p) {
+  if (!*p) return hipSuccess;
+  e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void*)*p), e->allocs.end());
+  const hipError_t err = hipFree(*p);
+  *p = nullptr;
+  return err;
+}
+
+}  // namespace
 
 // every launch of the integrator and the observables (launch_*, run_bd,
 // vision_cone_impl, launch_field, the LDS sizes and their opt-in)
@@ -283,34 +244,37 @@ struct swarm_engine {
 
 namespace {
 
-// SWARMRL_AMD_* overrides of a path choice of swarm_engine_create, by the
-// first character of a set variable's value.
-// "0" clears; anything else leaves *v as it is.
-void env_clears(const char* name, bool* v) {
-  const char* s = std::getenv(name);
-  if (s && s[0] == '0') *v = false;
-}
-// "0" clears, "1" sets; anything else leaves *v as it is.
-void env_clears_or_sets(const char* name, bool* v) {
-  const char* s = std::getenv(name);
-  if (s && s[0] == '0') *v = false;
-  if (s && s[0] == '1') *v = true;
-}
-// Set at all: "0" clears, anything else sets.
-void env_sets_unless_0(const char* name, bool* v) {
-  if (const char* s = std::getenv(name)) *v = s[0] != '0';
+// The SWARMRL_AMD_* overrides of swarm::plan_engine, read here and nowhere
+// else: the first character of each variable's value, 0 for unset (an empty
+// value is set: it counts as a blank).
+swarm::PlanOverrides read_plan_overrides() {
+  auto first = [](const char* name) -> char {
+    const char* s = std::getenv(name);
+    return !s ? 0 : s[0] ? s[0] : ' ';
+  };
+  swarm::PlanOverrides ov;
+  ov.cluster_path = first("SWARMRL_AMD_CLUSTER_PATH");
+  ov.local_uf = first("SWARMRL_AMD_LOCAL_UF");
+  ov.nlist = first("SWARMRL_AMD_NLIST");
+  ov.noise_table = first("SWARMRL_AMD_NOISE_TABLE");
+  ov.env_build = first("SWARMRL_AMD_ENV_BUILD");
+  ov.wide_run = first("SWARMRL_AMD_WIDE_RUN");
+  ov.rot_helper = first("SWARMRL_AMD_ROT_HELPER");
+  ov.defer_check = first("SWARMRL_AMD_DEFER_CHECK");
+  return ov;
 }
 
-template <typename T>
-int dev_alloc(swarm_engine* e, T** p, size_t count) {
-  if (e->n_allocs >= (int)(sizeof(e->allocs) / sizeof(e->allocs[0])))
-    return fail(SWARM_ECAPACITY, "engine allocation table full");
-  void* v = nullptr;
-  HIP_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-  HIP_TRY(hipMemsetAsync(v, 0, std::max<size_t>(count, 1) * sizeof(T), e->stream));
-  e->allocs[e->n_allocs++] = v;
-  *p = reinterpret_cast<T*>(v);
-  return SWARM_OK;
+// One row of swarm_engine_create's allocation table (SWARM_ENGINE_BUFS,
+// swarm_plan.h): the member that takes the buffer, and its element size.
+struct BufSlot {
+  void** member;
+  size_t elem;
+};
+template <swarm::EngineBuf kId, typename T>
+BufSlot buf_slot(T** member) {
+  static_assert(kId == swarm::kBufDerived || swarm::kBufElemBytes[kId] == sizeof(T),
+                "swarm_plan.h: a row's bytes per element disagree with the member's type");
+  return {reinterpret_cast<void**>(member), sizeof(T)};
 }
 
 void to_fixed(double x, double L, uint32_t* q, int32_t* img) {
@@ -377,306 +341,93 @@ const char* swarm_last_error(void) { return g_err.c_str(); }
 #endif
 const char* swarm_build_id(void) { return SWARM_BUILD_ID; }
 
+// the plan's static_lds
+static_assert(swarm::kPairTablesBytes == sizeof(swarm::PairTables), "swarm_sizes.h: PairTables");
+
 int swarm_engine_create(const swarm_params_t* params, int32_t n_envs, int32_t n_particles,
                         const int32_t* species, swarm_engine_t** out) {
-  if (!params || !out) return fail(SWARM_EINVAL, "null argument");
+  // 1. the arguments
+  if (!params || !out || !species) return fail(SWARM_EINVAL, "null argument");
   *out = nullptr;
-  if (params->n_dims != 2 && params->n_dims != 3)
-    return fail(SWARM_EINVAL, "n_dims must be 2 or 3");
-  if (n_envs < 1 || n_particles < 1) return fail(SWARM_EINVAL, "n_envs and n_particles must be >= 1");
-  if (params->n_species < 1 || params->n_species > kMaxSpecies)
-    return fail(SWARM_EINVAL, "n_species out of range");
-  for (int a = 0; a < params->n_dims; ++a)
-    if (!(params->box[a] > 0.0)) return fail(SWARM_EINVAL, "box lengths must be positive");
-  // the run kernels' 1/r^2 (rcp_rn) is exact for r^2 in [2^-96, 2^96]: a
-  // fixed-point grid step of at least 2^-48 and radii below 2^40
-  for (int a = 0; a < params->n_dims; ++a)
-    if (!(params->box[a] >= 0x1p-16)) return fail(SWARM_EINVAL, "box lengths must be >= 2^-16");
-  if (!(params->time_step > 0.0)) return fail(SWARM_EINVAL, "time_step must be positive");
-  for (int s = 0; s < params->n_species; ++s) {
-    if (!(params->gamma_t[s] > 0.0) || !(params->gamma_r[s] > 0.0) || !(params->radius[s] >= 0.0))
-      return fail(SWARM_EINVAL, "friction coefficients must be positive");
-    if (!(params->radius[s] < 0x1p40)) return fail(SWARM_EINVAL, "radius must be < 2^40");
-  }
-  if (n_particles > (1 << 20))
-    return fail(SWARM_ECAPACITY, "more than 2^20 particles per env are not supported");
+
+  // 2. the plan (its parameter checks first), then what it does not see:
+  // the species indices and the device
+  swarm::EnginePlan plan;
+  const char* msg = "";
+  if (const int rc = swarm::plan_engine(*params, n_envs, n_particles, read_plan_overrides(),
+                                        swarm::kPairTablesBytes, &plan, &msg))
+    return fail(rc, msg);
   for (int i = 0; i < n_particles; ++i)
     if (species[i] < 0 || species[i] >= params->n_species)
       return fail(SWARM_EINVAL, "species index out of range");
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) return fail(SWARM_EDEVICE, "no HIP device");
 
+  // 3. the plan into the kernels' arguments
   swarm_engine* e = new swarm_engine();
   e->params = *params;
   derive(*params, e->derived);
   e->n_envs = n_envs;
   e->n = n_particles;
-  if (hipGetDevice(&e->device) != hipSuccess) {
-    delete e;
-    return fail(SWARM_EDEVICE, "no HIP device");
-  }
-  const bool three_d = params->n_dims == 3;
-  if (three_d)
-    cell_grid3(*params, n_particles, e->derived.rc_max, &e->lxg, &e->lyg, &e->lzg);
-  else
-    cell_grid(*params, n_particles, e->derived.rc_max, &e->lxg, &e->lyg);
-  if (three_d)
-    cell_grid3(*params, n_particles, e->derived.rc_max + skin_um(), &e->lxb, &e->lyb, &e->lzb);
-  else
-    cell_grid(*params, n_particles, e->derived.rc_max + skin_um(), &e->lxb, &e->lyb);
-  const int lcb = e->lxb + e->lyb + e->lzb;  // build cells 2^lcb
-  // static LDS of the kernels: pair tables (k_global, k_check, k_cluster_run)
-  // and the link table of k_cluster_build
-  constexpr size_t kStaticLds = sizeof(swarm::PairTables);
-  if (check_lds_bytes(e->lxg, e->lyg, n_particles, params->n_dims) + kStaticLds > kMaxLds) {
-    delete e;
-    return fail(SWARM_ECAPACITY, "env cell grid does not fit the LDS of one workgroup");
-  }
-  // the cluster path needs the build workgroup's LDS and a non-degenerate
-  // build grid; otherwise every window runs on the global path
-  e->big_build = build_is_big(n_particles);
-  e->sc.pair_cap = build_pair_cap(n_particles, e->big_build);
-  // non-periodic boxes run windowed in 2-D and 3-D (edge cells and
-  // unwrapped distances in the build and the exact check; a listed pair's
-  // folded difference is its unwrapped one), the neighbour-list window is
-  // periodic-only; SWARMRL_AMD_CLUSTER_PATH=0 forces the global path (A/B
-  // and parity)
-  e->sc.periodic = params->periodic ? 1 : 0;
-  // block-local union-find in the 2-D pair search (SWARMRL_AMD_LOCAL_UF=0|1;
-  // default: for envs above 4096 colloids, whose one-workgroup union phase
-  // is long; at 4096 the pair search's block barriers cost more than the
-  // union saves, measured)
-  bool local_uf = n_particles > 4096;
-  env_sets_unless_0("SWARMRL_AMD_LOCAL_UF", &local_uf);
-  e->sc.local_uf = local_uf ? 1 : 0;
-  e->sc.rstamp = nullptr;
-  e->sc.multi_species = params->n_species > 1 ? 1 : 0;
-  // the 2-D build sort stages its scatter in LDS: the sorted rows of up to
-  // K entries per pass beside the cell counts (K a multiple of 4, at least
-  // N / 4)
-  {
-    const size_t counts = (16 + ((size_t)1 << (e->lxb + e->lyb)) + 1) * 4;
-    const size_t room = counts + 4096 < kMaxLds ? kMaxLds - counts - 4096 : 0;
-    const size_t k = std::min((size_t)n_particles, room / 12) & ~(size_t)3;
-    e->sc.sort_stage_k = params->n_dims == 2 && n_particles <= 16 * 1024 &&
-                                 4 * k >= (size_t)n_particles
-                             ? (int32_t)k
-                             : 0;
-  }
-  e->cluster_path = e->sc.pair_cap >= n_particles &&
-                    n_particles < 65536 &&
-                    swarm::build_lds_words_big(n_particles) * 4 <= kMaxLds &&
-                    (size_t)(16 + (1 << lcb) + 1) * 4 <= kMaxLds &&
-                    (1 << e->lxb) >= 3 && (1 << e->lyb) >= 3 && (!three_d || (1 << e->lzb) >= 3) &&
-                    (!three_d || check3_lds_bytes(e) <= kMaxLds);
-  env_clears("SWARMRL_AMD_CLUSTER_PATH", &e->cluster_path);
-  if (e->cluster_path) {
-    // mean number of colloids within 2 r_max + skin of one (deg): above ~2
-    // in 3-D, ~3 in 2-D the links percolate into clusters wider than a wave
-    // (3-D: re-run on the global path; 2-D: k_check's one-workgroup big
-    // cluster run, then the global path), so the window runs on the
-    // neighbour-list path instead.  SWARMRL_AMD_NLIST=0|1 overrides.
-    double rmax = 0.0;
-    for (int s = 0; s < params->n_species; ++s) rmax = std::max(rmax, params->radius[s]);
-    const double link = 2.0 * rmax + skin_um();
-    const double deg =
-        three_d ? (double)n_particles / (params->box[0] * params->box[1] * params->box[2]) *
-                      (2.0 / 3.0) * kTwoPi * link * link * link
-                : (double)n_particles / (params->box[0] * params->box[1]) * 0.5 * kTwoPi * link *
-                      link;
-    e->nlist_path = deg > (three_d ? 2.0 : 3.0);
-    env_clears_or_sets("SWARMRL_AMD_NLIST", &e->nlist_path);
-    if (!params->periodic) e->nlist_path = false;  // the Verlet-list window is periodic-only
-  }
+  e->device = device;
+  e->plan = plan;
   const size_t M = (size_t)n_envs * n_particles;
-  int rc = SWARM_OK;
-  rc = rc ? rc : dev_alloc(e, &e->st.q, 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.img, 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.ang, M);
-  rc = rc ? rc : dev_alloc(e, &e->st.f_swim, M);
-  rc = rc ? rc : dev_alloc(e, &e->st.torque_z, M);
-  rc = rc ? rc : dev_alloc(e, &e->st.f_ext, 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.vel, 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.omega, M);
-  e->own_f_swim = e->st.f_swim;
-  e->own_torque_z = e->st.torque_z;
-  rc = rc ? rc : dev_alloc(e, &e->st.species, (size_t)n_particles);
-  rc = rc ? rc : dev_alloc(e, &e->d_derived, 1);
-  rc = rc ? rc : dev_alloc(e, &e->d_box, 3);
-  rc = rc ? rc : dev_alloc(e, &e->d_order, M);
-  rc = rc ? rc : dev_alloc(e, &e->d_count, 1);
-  rc = rc ? rc : dev_alloc(e, &e->d_step, swarm::kCtlWords);
-  rc = rc ? rc : dev_alloc(e, &e->d_arrive, 1);
-  // integrator scratch
-  // One pair pass per wave and sub-step (k_cluster_build): the run kernel
-  // lasts as long as its slowest waves, at any env count.  Latency-bound
-  // launches (few envs x particles fill few SIMDs) also read their normals
-  // from a table (k_noise; SWARMRL_AMD_NOISE_TABLE=0|1 overrides).
-  const bool latency_bound = (long)n_envs * n_particles <= 32768;
-  e->sc.one_pass = 1;
-  // fewer, fuller waves only pay when the waves compete for the SIMDs; a
-  // latency-bound launch has SIMDs to spare and a shorter build is worth more
-  e->sc.fill_singletons = latency_bound ? 0 : 1;
-  const int S = swarm::slots_per_env(n_particles, e->sc.one_pass != 0);
-  e->sc.S = S;
-  e->sc.wmax = S / 64;
-  rc = rc ? rc : dev_alloc(e, &e->sc.sqx, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.sqy, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.sqz, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.simg, params->periodic ? 1 : 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.dir3, 3 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.torque_xy, 2 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.omega_xy, 2 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.wall_viol, 1);
-  rc = rc ? rc : dev_alloc(e, &e->st.f_prev, 2 * M);  // two slots (window parity)
-  rc = rc ? rc : dev_alloc(e, &e->st.tz_prev, 2 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.ang_prev, 2 * M);
-  rc = rc ? rc : dev_alloc(e, &e->st.dir3_prev, three_d ? 6 * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->st.txy_prev, three_d ? 4 * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.nmov, (size_t)n_envs);
-  rc = rc ? rc : dev_alloc(e, &e->sc.movers, (size_t)n_envs * swarm::kMaxMovers);
-  rc = rc ? rc : dev_alloc(e, &e->sc.sidx, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bq, (three_d ? 3 : 2) * M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bimg, (three_d ? 3 : 2) * M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bdir3, three_d ? 3 * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bang, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.root, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.slot_of, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.perm, (size_t)n_envs * S);
-  rc = rc ? rc : dev_alloc(e, &e->sc.pairs, (size_t)n_envs * (S / 64) * swarm::kPairsPerWave);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bsq, (three_d ? 3 : 2) * M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.nl, e->nlist_path ? (size_t)swarm::kNlMax * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.nn, e->nlist_path ? M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.qalt, e->nlist_path ? (three_d ? 3 : 2) * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.qa, e->nlist_path ? 2 * M : 1);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bsid, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.bcstart, (size_t)n_envs * ((1 << lcb) + 1));
-  rc = rc ? rc : dev_alloc(e, &e->sc.gplist, (size_t)n_envs * std::max(e->sc.pair_cap, 1));
-  rc = rc ? rc : dev_alloc(e, &e->sc.xpairs, (size_t)n_envs * std::max(e->sc.pair_cap, 1));
-  rc = rc ? rc : dev_alloc(e, &e->sc.lroot, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.gnx, (size_t)n_envs);
-  // chip-wide build sort of large 2-D envs (k_sort_count/scan/scatter):
-  // per-cell counters (zero between builds) and each particle's cell / rank
-  e->chip_sort = params->n_dims == 2 && n_particles > 4096;
-  if (e->chip_sort) {
-    rc = rc ? rc : dev_alloc(e, &e->sc.gcnt, (size_t)n_envs << (e->lxb + e->lyb));
-    rc = rc ? rc : dev_alloc(e, &e->sc.gcell, M);
-    rc = rc ? rc : dev_alloc(e, &e->sc.grank, M);
-  }
-  rc = rc ? rc : dev_alloc(e, &e->sc.gnpairs, (size_t)n_envs);
-  // 2-D envs of the large-N build after the block-local pair search: the
-  // build spread over the chip (k_mwb_*) instead of one workgroup, with a
-  // fourth per-particle word (the offset of its pairs in the pair list)
-  e->sc.bmisc = nullptr;
-  const bool mwb = e->big_build && params->n_dims == 2 && e->sc.local_uf;
-  if (e->big_build) rc = rc ? rc : dev_alloc(e, &e->sc.gclus, (mwb ? 4 : 3) * M);
-  if (mwb) rc = rc ? rc : dev_alloc(e, &e->sc.bmisc, (size_t)n_envs * swarm::kBmWords);
-  rc = rc ? rc : dev_alloc(e, &e->sc.wave_npairs, (size_t)n_envs * (S / 64));
-  rc = rc ? rc : dev_alloc(e, &e->sc.phase, 32 + 4 * (size_t)n_envs * (S / 64));
-  rc = rc ? rc : dev_alloc(e, &e->sc.disp, M);
-  rc = rc ? rc : dev_alloc(e, &e->sc.env_waves, (size_t)n_envs);
-  rc = rc ? rc : dev_alloc(e, &e->sc.fallback, (size_t)n_envs);
-  rc = rc ? rc : dev_alloc(e, &e->sc.big_list, (size_t)n_envs * swarm::kBigMax);
-  rc = rc ? rc : dev_alloc(e, &e->sc.big_pairs, (size_t)n_envs * swarm::kBigPairs);
-  rc = rc ? rc : dev_alloc(e, &e->sc.big_n, (size_t)n_envs);
-  rc = rc ? rc : dev_alloc(e, &e->sc.big_np, (size_t)n_envs);
-  rc = rc ? rc : dev_alloc(e, &e->vs.rec, 2 * M);
-  rc = rc ? rc : dev_alloc(e, &e->vs.agent_row, (size_t)n_particles);
-  // noise table for latency-bound windows: few envs fill few SIMDs, so the
-  // normals are better produced chip-wide ahead of the run.
-  {
-    bool want = latency_bound;
-    env_clears_or_sets("SWARMRL_AMD_NOISE_TABLE", &want);
-    // 3-D and neighbour-list windows draw their normals in the kernels
-    e->noise_table = want && e->derived.noisy && e->cluster_path && !three_d && !e->nlist_path;
-    if (e->noise_table)
-      rc = rc ? rc : dev_alloc(e, &e->d_noise, 2 * swarm::noise_table_words(M));
-    // the one-launch build (one CU per env) for throughput-bound engines
-    // when its sort region fits below the pair list; latency-bound ones keep
-    // the three-launch build, whose pair search spreads over the chip
-    // (one env: 42 us for the three launches, 52 us for k_build_env)
-    {
-      const int wm = S / 64;
-      const size_t below = 16 + 16 + 3 * 68 + (size_t)((wm + 3) & ~3) + 4 * (size_t)n_particles;
-      const bool can = e->cluster_path && !e->big_build && !three_d && !e->nlist_path &&
-                       params->periodic &&
-                       swarm::build_env_sort_words(n_particles, 1 << (e->lxb + e->lyb)) <= below;
-      bool want_env = !latency_bound;
-      env_clears_or_sets("SWARMRL_AMD_ENV_BUILD", &want_env);
-      e->env_build = can && want_env;
-    }
-    // one block per CU for latency-bound runs; beside a run of up to 16384
-    // particles, 64 CUs produce the next window's table in its shadow (C5:
-    // no k_noise launch between the policy and the run)
-    e->wide_run = e->noise_table;
-    env_clears("SWARMRL_AMD_WIDE_RUN", &e->wide_run);
-    // (32 noise workgroups above 4096 colloids, so that C4's 8 x 1024 gets one
-    // run wave per CU, measured slower: C4 81.1 -> 72.9 M, same box)
-    e->noise_blocks = e->wide_run && M <= 16384 ? 64 : 0;
-    env_clears("SWARMRL_AMD_ROT_HELPER", &e->rot_helper);
-    // run waves per CU: a wave alone on its CU does not share the CU's
-    // texture path with other waves' scattered noise-table gathers; four per
-    // CU once the run's waves (~1 per 46 particles) would not fit one per CU
-    {
-      const long est = (long)M / 46 + 1;
-      e->run_wpb = est + e->noise_blocks <= 224 ? 1 : (est / 2 + e->noise_blocks <= 256 ? 2 : 4);
-    }
-    // l1_pairs: the ride-along build's pair search moves into the slice's
-    // first launch as a filter of candidate lists prepared during the last
-    // run (periodic 2-D, the plain pair search, a build grid of at least 5
-    // cells a side for the 5 x 5 candidate stencil)
-    e->sc.l1_pairs = e->wide_run && e->cluster_path && !e->nlist_path && !e->env_build &&
-                             !e->big_build && !three_d && params->periodic && !e->sc.local_uf &&
-                             (1 << e->lxb) >= 5 && (1 << e->lyb) >= 5
-                         ? 1
-                         : 0;
-    if (e->sc.l1_pairs) {
-      // widening of the candidate radius: up to 1.5 um of motion per window
-      // (the bench's swimmers move ~0.3 um; > 1.5 um is a > 6 sigma event),
-      // at most half a cell side (the 5 x 5 stencil) and at least skin / 2
-      // (k_check sees every particle that moved more: the movers)
-      const double side = std::min(params->box[0] / (1 << e->lxb), params->box[1] / (1 << e->lyb));
-      const double cd = std::max(0.5 * skin_um(), std::min(1.5, 0.5 * side));
-      e->derived.cand_disp = (float)cd;
-      for (int a = 0; a < params->n_species; ++a)
-        for (int b = 0; b < params->n_species; ++b) {
-          const double r = params->radius[a] + params->radius[b] + skin_um() + 2.0 * cd;
-          e->derived.nbc2[a * kMaxSpecies + b] = (float)(r * r);
-        }
-      rc = rc ? rc : dev_alloc(e, &e->sc.cand, (size_t)swarm::kCandMax * M);
-      rc = rc ? rc : dev_alloc(e, &e->sc.ncand, M);
-    }
-    rc = rc ? rc : dev_alloc(e, &e->sc.cand_ok, (size_t)n_envs);
-    rc = rc ? rc : dev_alloc(e, &e->sc.cand_ovf, (size_t)n_envs);
-    rc = rc ? rc : dev_alloc(e, &e->sc.sort_done, (size_t)n_envs);
-    rc = rc ? rc : dev_alloc(e, &e->sc.stats, 4);
-    if (e->sc.l1_pairs) {
-      // a check that rides in the reward launch: window numbers, verdicts
-      // and the outcome counters in one allocation
-      uint64_t* w = nullptr;
-      rc = rc ? rc : dev_alloc(e, &w, 3 * (size_t)n_envs + 4);
-      if (!rc) {
-        e->sc.vtag = w;
-        e->sc.verdict = w + n_envs;
-        e->sc.varrive = w + 2 * (size_t)n_envs;
-        e->sc.cstats = reinterpret_cast<unsigned long long*>(w + 3 * (size_t)n_envs);
-      }
-      // (a pattern of its own: set at all, only "1" sets)
-      const char* dc = std::getenv("SWARMRL_AMD_DEFER_CHECK");
-      e->defer_check = dc ? dc[0] == '1' : kDeferCheckDefault;
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess)
-        e->n_cus = cus;
-    }
-
-  }
-  allow_engine_lds(e->device);
-  if (rc) {
-    swarm_engine_destroy(e);
-    return rc;
-  }
   e->st.n = n_particles;
   e->st.m = (int32_t)M;
   e->st.dims = params->n_dims;
   e->st.reuse = params->reuse_forces ? 1 : 0;
+  e->sc.pair_cap = plan.pair_cap;
+  e->sc.periodic = params->periodic ? 1 : 0;
+  e->sc.local_uf = plan.local_uf ? 1 : 0;
+  e->sc.multi_species = params->n_species > 1 ? 1 : 0;
+  e->sc.sort_stage_k = plan.sort_stage_k;
+  e->sc.one_pass = plan.one_pass ? 1 : 0;
+  e->sc.fill_singletons = plan.fill_singletons ? 1 : 0;
+  e->sc.S = plan.S;
+  e->sc.wmax = plan.wmax;
+  e->sc.l1_pairs = plan.l1_pairs ? 1 : 0;
+  if (plan.l1_pairs) {
+    e->derived.cand_disp = (float)plan.cand_disp;
+    for (int a = 0; a < params->n_species; ++a)
+      for (int b = 0; b < params->n_species; ++b) {
+        const double r = params->radius[a] + params->radius[b] + kSkinUm + 2.0 * plan.cand_disp;
+        e->derived.nbc2[a * kMaxSpecies + b] = (float)(r * r);
+      }
+    // (launch_field: a check rides in the reward launch while every
+    // workgroup of the launch is resident)
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess)
+      e->n_cus = cus;
+  }
+
+  // 4. the buffers the plan lists, zeroed, in the plan's order
+  uint64_t* vcheck = nullptr;
+#define SWARM_BUF_SLOT(id, bytes, member, elements) buf_slot<swarm::kBuf##id>(&member),
+  const BufSlot slots[swarm::kNumEngineBufs] = {SWARM_ENGINE_BUFS(SWARM_BUF_SLOT)};
+#undef SWARM_BUF_SLOT
+  hipError_t err = hipSuccess;
+  for (int k = 0; k < swarm::kNumEngineBufs && err == hipSuccess; ++k) {
+    const BufSlot& s = slots[k];
+    const size_t bytes = plan.count[k] * s.elem;
+    if (bytes == 0) continue;  // not on this engine's paths
+    err = dev_malloc(e, s.member, bytes);
+    if (err == hipSuccess) err = hipMemsetAsync(*s.member, 0, bytes, e->stream);
+  }
+  allow_engine_lds(device);
+  if (err != hipSuccess) {
+    swarm_engine_destroy(e);
+    return fail(SWARM_EDEVICE, std::string("engine buffers: ") + hipGetErrorString(err));
+  }
+  e->own_f_swim = e->st.f_swim;
+  e->own_torque_z = e->st.torque_z;
+  if (vcheck) {
+    e->sc.vtag = vcheck;
+    e->sc.verdict = vcheck + n_envs;
+    e->sc.varrive = vcheck + 2 * (size_t)n_envs;
+    e->sc.cstats = reinterpret_cast<unsigned long long*>(vcheck + 3 * (size_t)n_envs);
+  }
+
+  // 5. the upload
   std::vector<uint8_t> sp(n_particles);
   for (int i = 0; i < n_particles; ++i) sp[i] = (uint8_t)species[i];
   if (hipMemcpy(e->st.species, sp.data(), sp.size(), hipMemcpyHostToDevice) != hipSuccess ||
@@ -694,19 +445,13 @@ void swarm_engine_destroy(swarm_engine_t* e) {
   if (!e) return;
   (void)flush_check(e);
   (void)hipDeviceSynchronize();
-  if (e->d_tstamp) (void)hipFree(e->d_tstamp);
-  if (e->d_rstamp) (void)hipFree(e->d_rstamp);
   for (auto* v : {&e->prof_events, &e->graph_events, &e->graph_cal})
     for (auto& pr : *v) {
       (void)hipEventDestroy(pr.first);
       (void)hipEventDestroy(pr.second);
     }
-  for (int k = 0; k < e->n_allocs; ++k) (void)hipFree(e->allocs[k]);
-  if (e->d_start) (void)hipFree(e->d_start);
-  if (e->d_pairs) (void)hipFree(e->d_pairs);
-  if (e->d_pot) (void)hipFree(e->d_pot);
+  for (void* p : e->allocs) (void)hipFree(p);
   if (e->traj_host) (void)hipHostFree(e->traj_host);
-  if (e->d_traj_count) (void)hipFree(e->d_traj_count);
   delete e;
 }
 
@@ -933,11 +678,11 @@ int swarm_engine_profile(swarm_engine_t* e, int32_t enable, double* run_ms, int3
   e->profile = enable != 0;
   // the launch stamps of captured run nodes (allocated here: never under capture)
   if (e->profile && !e->d_tstamp)
-    HIP_TRY(hipMalloc(&e->d_tstamp, 2 * (size_t)kMaxStamps * swarm::kStampSub *
-                                        sizeof(unsigned long long)));
+    HIP_TRY(dev_malloc(e, &e->d_tstamp, 2 * (size_t)kMaxStamps * swarm::kStampSub *
+                                            sizeof(unsigned long long)));
   if (e->profile && !e->d_rstamp)
-    HIP_TRY(hipMalloc(&e->d_rstamp, 2 * (size_t)kMaxStamps * swarm::kRoles * swarm::kStampSub *
-                                        sizeof(unsigned long long)));
+    HIP_TRY(dev_malloc(e, &e->d_rstamp, 2 * (size_t)kMaxStamps * swarm::kRoles *
+                                            swarm::kStampSub * sizeof(unsigned long long)));
   if (!e->profile) e->sc.rstamp = nullptr;
   return rc;
 }
@@ -1086,7 +831,7 @@ int swarm_engine_time_run(swarm_engine_t* e, int32_t n_steps, int32_t reps, doub
   if (const int frc = flush_check(e)) return frc;
   if (n_steps < 1 || n_steps > swarm::kMaxWindow || reps < 1)
     return fail(SWARM_EINVAL, "1 <= n_steps <= 128 and reps >= 1");
-  if (!e->cluster_path || e->nlist_path || e->params.n_dims != 2)
+  if (!e->plan.cluster_path || e->plan.nlist_path || e->params.n_dims != 2)
     return fail(SWARM_ESTATE, "swarm_engine_time_run times the 2-D cluster window only");
   if (e->prebuilt) {  // a pending side-stream build would race with this one
     HIP_TRY(hipDeviceSynchronize());
@@ -1094,7 +839,7 @@ int swarm_engine_time_run(swarm_engine_t* e, int32_t n_steps, int32_t reps, doub
   }
   e->ride_stage = 0;  // a deferred build is superseded by the one below
   int rc = launch_build(e, e->stream);
-  if (!rc && e->noise_table && !e->next_table_ready) rc = launch_noise(e, e->stream, n_steps);
+  if (!rc && e->plan.noise_table && !e->next_table_ready) rc = launch_noise(e, e->stream, n_steps);
   if (rc) return rc;
   hipEvent_t ev0, ev1;
   HIP_TRY(hipEventCreate(&ev0));
@@ -1142,7 +887,7 @@ int swarm_engine_prebuild(swarm_engine_t* e, void* stream, int32_t n_steps_hint)
   if (!e) return fail(SWARM_EINVAL, "null engine");
   if (const int frc = flush_check(e)) return frc;
   if (n_steps_hint < 0) return fail(SWARM_EINVAL, "n_steps_hint must be >= 0");
-  if (!e->cluster_path) return SWARM_OK;  // the global path has no build step
+  if (!e->plan.cluster_path) return SWARM_OK;  // the global path has no build step
   const int rc = launch_build(e, stream ? reinterpret_cast<hipStream_t>(stream) : e->stream);
   if (rc) return rc;
   e->prebuilt = true;
@@ -1153,7 +898,7 @@ int swarm_engine_prebuild_noise(swarm_engine_t* e, void* stream, int32_t n_steps
   if (!e) return fail(SWARM_EINVAL, "null engine");
   if (const int frc = flush_check(e)) return frc;
   if (n_steps_hint < 0) return fail(SWARM_EINVAL, "n_steps_hint must be >= 0");
-  if (!e->noise_table || n_steps_hint == 0) return SWARM_OK;
+  if (!e->plan.noise_table || n_steps_hint == 0) return SWARM_OK;
   if (e->next_table_ready) return SWARM_OK;  // filled beside the last run
   const int n = std::min<int>(n_steps_hint, swarm::kMaxWindow);
   const int rc = launch_noise(e, stream ? reinterpret_cast<hipStream_t>(stream) : e->stream, n);
@@ -1181,7 +926,7 @@ int swarm_engine_build_stats(swarm_engine_t* e, uint64_t* out4, int32_t reset) {
 int swarm_engine_hint_defer_check(swarm_engine_t* e) {
   if (!e) return fail(SWARM_EINVAL, "null engine");
   if (const int frc = flush_check(e)) return frc;
-  e->defer_hint = e->defer_check;
+  e->defer_hint = e->plan.defer_check;
   return SWARM_OK;
 }
 
@@ -1238,7 +983,7 @@ int swarm_engine_traj_ring(swarm_engine_t* e, int32_t capacity, int32_t env, voi
     HIP_TRY(hipHostFree(e->traj_host));
     e->traj_host = e->traj_dev = nullptr;
   }
-  if (!e->d_traj_count) HIP_TRY(hipMalloc(&e->d_traj_count, sizeof(uint64_t)));
+  if (!e->d_traj_count) HIP_TRY(dev_malloc(e, &e->d_traj_count, sizeof(uint64_t)));
   HIP_TRY(hipMemset(e->d_traj_count, 0, sizeof(uint64_t)));
   const size_t eb = traj_entry_bytes(e->n, e->params.n_dims);
   const size_t bytes = 64 + eb * (size_t)capacity;
@@ -1545,7 +1290,7 @@ int swarm_engine_vision_policy(swarm_engine_t* e, const swarm_vision_params_t* v
   const swarm::MlpArgs m{features, (int)n, nb, w1, b1, hidden, w2, b2, k, (uint32_t)seed,
                          (uint32_t)(seed >> 32), reinterpret_cast<unsigned long long*>(agent_state),
                          explore_p, f_table, t_table, out_idx, out_logp, out_f, out_t, out_logits};
-  if (!e->wide_run) {
+  if (!e->plan.wide_run) {
     // throughput-bound engines (many envs): the cone is VALU-bound and the
     // MLP's four lanes per agent would lengthen every group; the two kernels
     // of the calls this replaces, the policy drawing with the first
@@ -1618,8 +1363,9 @@ int swarm_engine_neighbor_pairs(swarm_engine_t* e, int32_t env, double cutoff, i
   int rc = build_grid(e, lx, ly);
   if (rc) return rc;
   if ((size_t)max_pairs > e->pairs_cap) {
-    if (e->d_pairs) HIP_TRY(hipFree(e->d_pairs));
-    HIP_TRY(hipMalloc(&e->d_pairs, 2 * (size_t)std::max(max_pairs, 1) * sizeof(int32_t)));
+    e->pairs_cap = 0;
+    HIP_TRY(dev_free(e, &e->d_pairs));
+    HIP_TRY(dev_malloc(e, &e->d_pairs, 2 * (size_t)std::max(max_pairs, 1) * sizeof(int32_t)));
     e->pairs_cap = (size_t)max_pairs;
   }
   HIP_TRY(hipMemsetAsync(e->d_count, 0, sizeof(int32_t), e->stream));
@@ -1759,8 +1505,8 @@ int swarm_engine_set_potential_field(swarm_engine_t* e, const float* phi, int32_
     }
     if (words > e->pot_cap) {
       // the new copy first: a failed allocation leaves the old field in place
-      void* v = nullptr;
-      HIP_TRY(hipMalloc(&v, words * sizeof(float)));
+      float* v = nullptr;
+      HIP_TRY(dev_malloc(e, &v, words * sizeof(float)));
       if (e->d_pot) {
         // no kernel may find the old copy once it is freed: the device's
         // descriptor is cleared first, and the stream drained of its readers
@@ -1768,13 +1514,14 @@ int swarm_engine_set_potential_field(swarm_engine_t* e, const float* phi, int32_
         hipError_t err = hipMemcpyAsync(e->d_derived, &e->derived, sizeof(Derived),
                                         hipMemcpyHostToDevice, e->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-        if (err == hipSuccess) err = hipFree(e->d_pot);
+        if (err == hipSuccess) err = dev_free(e, &e->d_pot);
         if (err != hipSuccess) {
-          (void)hipFree(v);
+          (void)dev_free(e, &v);
+          if (!e->d_pot) e->pot_cap = 0;
           return fail(SWARM_EDEVICE, std::string("potential field: ") + hipGetErrorString(err));
         }
       }
-      e->d_pot = reinterpret_cast<float*>(v);
+      e->d_pot = v;
       e->pot_cap = (size_t)words;
     }
     HIP_TRY(hipMemcpyAsync(e->d_pot, records ? rec.data() : phi, words * sizeof(float),
@@ -1824,7 +1571,7 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   const double half = 0.5 * (rod->n - 1) * rod->delta;
   if (!(half < 0.49 * std::min(e->params.box[0], e->params.box[1])))
     return fail(SWARM_EINVAL, "the rod must be shorter than the box");
-  const size_t lds = swarm::rod_lds_words(e->n, 1 << (e->lxg + e->lyg)) * 4;
+  const size_t lds = swarm::rod_lds_words(e->n, 1 << (e->plan.lxg + e->plan.lyg)) * 4;
   if (lds + sizeof(swarm::PairTables) > kMaxLds)
     return fail(SWARM_ECAPACITY, "env does not fit the LDS of one workgroup");
   e->rod.first = rod->first;
@@ -1832,13 +1579,14 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   e->rod.delta = (float)rod->delta;
   e->rod.fixed = rod->fixed ? 1 : 0;
   e->has_rod = true;
-  // no cluster windows, and none of what prepares or checks them
-  e->cluster_path = false;
-  e->nlist_path = false;
-  e->noise_table = false;
-  e->wide_run = false;
-  e->env_build = false;
-  e->defer_check = false;
+  // no cluster windows, and none of what prepares or checks them: the one
+  // place that rewrites the plan after creation
+  e->plan.cluster_path = false;
+  e->plan.nlist_path = false;
+  e->plan.noise_table = false;
+  e->plan.wide_run = false;
+  e->plan.env_build = false;
+  e->plan.defer_check = false;
   e->defer_hint = false;
   e->prebuilt = false;
   e->prebuilt_noise_steps = 0;
@@ -1874,8 +1622,9 @@ int swarm_engine_defer_build(swarm_engine_t* e, int32_t* deferred) {
   *deferred = 0;
   // the three-launch 2-D cluster build of a latency-bound engine only (the
   // stages the fused observable / policy launches know how to carry)
-  const bool ok = e->cluster_path && !e->nlist_path && !e->env_build && !e->big_build &&
-                  e->params.n_dims == 2 && e->wide_run;
+  const swarm::EnginePlan& pl = e->plan;
+  const bool ok = pl.cluster_path && !pl.nlist_path && !pl.env_build && !pl.big_build &&
+                  e->params.n_dims == 2 && pl.wide_run;
   if (!ok) return SWARM_OK;
   e->prebuilt = false;
   e->ride_stage = 1;

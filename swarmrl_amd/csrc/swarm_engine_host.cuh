@@ -3,10 +3,11 @@
 // ("Host launch layer").
 //
 // Part of swarm_engine.hip's translation unit, included after struct
-// swarm_engine: everything here takes the engine and uses fail, HIP_TRY and
-// cell_grid.  swarm_engine.hip keeps the C ABI (argument checks, engine state,
-// uploads and downloads); what it launches beyond single fixed kernels it
-// launches through here.
+// swarm_engine: everything here takes the engine and uses fail, HIP_TRY,
+// dev_malloc / dev_free and cell_grid; what creation fixed it reads from
+// e->plan (swarm_plan.h).  swarm_engine.hip keeps the C ABI (argument checks,
+// engine state, uploads and downloads); what it launches beyond single fixed
+// kernels it launches through here.
 //
 // Every decision that picks a kernel or sizes a launch is taken in one place:
 //   *_lds_bytes       the dynamic LDS of each kernel family
@@ -32,48 +33,21 @@ using swarm_select::kVisionGWide;
 
 // ---- dynamic LDS
 
-constexpr size_t kMaxLds = 160 * 1024;
-
-// k_global: wave sums, cell counts and (2-D, N <= 4096) the register-resident
-// path's sorted copy
-size_t global_lds_bytes(int lx, int ly, int n, int dims) {
-  return (16 + (size_t)(1 << (lx + ly)) + 1 + swarm::global_lds_extra_words(n, dims, 1 << (lx + ly))) * 4;
-}
-
-// Pair-list capacity of the cluster build: up to 3 N pairs (mean degree 6),
-// at least N, within the LDS left after the other arrays of k_cluster_build;
-// 3 N in global memory for the large-N variant.
-int build_pair_cap(int n, bool big) {
-  if (big) return 3 * n;
-  const size_t fixed = swarm::build_lds_words(n, 0) * 4;
-  const size_t room = fixed < kMaxLds ? (kMaxLds - fixed) / 4 : 0;
-  return (int)std::min<size_t>(room, 3 * (size_t)n);
-}
-
-// The LDS build needs room for at least N pairs; beyond that, the large-N
-// variant keeps only the union-find forest in LDS.
-bool build_is_big(int n) { return swarm::build_lds_words(n, n) * 4 > kMaxLds; }
+// the formulas the plan shares with the kernels' layouts: swarm_sizes.h
+using swarm::kMaxLds;
+using swarm::check_lds_bytes;
+using swarm::global_lds_bytes;
 
 size_t build_lds_bytes(int n, int pair_cap) { return swarm::build_lds_words(n, pair_cap) * 4; }
 
-size_t check_lds_bytes(int lx, int ly, int n, int dims) {
-  // the global-path re-run region (cell counts + LDS path) or the big
-  // clusters' positions and force sums, after 16 + 16 + 1024 words
-  const size_t rerun = (size_t)(1 << (lx + ly)) + 1 + swarm::global_lds_extra_words(n, dims, 1 << (lx + ly));
-  const size_t big = 6 * (size_t)swarm::kBigMax + 2;  // uint2 positions, 2 x u64 sums
-  return (16 + 16 + 1024 + std::max(rerun, big)) * 4;
-}
-
-// k_check3: wave sums, misc, movers, then the 3-D global path's cell counts
 size_t check3_lds_bytes(const swarm_engine* e) {
-  return (16 + 16 + (size_t)swarm::kMaxMovers + (size_t)(1 << (e->lxg + e->lyg + e->lzg)) + 1) * 4;
+  const swarm::EnginePlan& pl = e->plan;
+  return swarm::check3_lds_bytes(pl.lxg, pl.lyg, pl.lzg);
 }
 
-// k_build_sort (and the fused launches carrying it): wave sums, cell counts
-// and, staged, the sorted x | y | id rows.
 size_t sort_lds_bytes(const swarm_engine* e) {
-  const size_t ncb = (size_t)1 << (e->lxb + e->lyb + e->lzb);
-  return (16 + ((ncb + 4) & ~(size_t)3) + 3 * (size_t)e->sc.sort_stage_k) * 4;
+  const swarm::EnginePlan& pl = e->plan;
+  return swarm::sort_lds_bytes(pl.lxb, pl.lyb, pl.lzb, e->sc.sort_stage_k);
 }
 
 // LDS of the vision grid's workgroup: wave sums, cell counts and, staged,
@@ -86,7 +60,7 @@ size_t vision_grid_lds_bytes(int lx, int ly, int n, bool staged) {
 // LDS of a launch carrying the l1_pairs pair search (its fallback tables)
 // beside workgroups that need `other` bytes.
 size_t l1_launch_lds(const swarm_engine* e, size_t other) {
-  return e->sc.l1_pairs ? std::max(other, l1_role_lds_bytes()) : other;
+  return e->sc.l1_pairs ? std::max(other, swarm::l1_role_lds_bytes()) : other;
 }
 
 // ROCm admits dynamic LDS up to the device limit at launch; this attribute
@@ -140,25 +114,26 @@ void allow_engine_lds(int device) {
 // ---- the global path, the rod, the noise table
 
 int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) {
+  const swarm::EnginePlan& pl = e->plan;
   if (e->params.n_dims == 3) {
     hipLaunchKernelGGL(swarm::k_global3, dim3(e->n_envs), dim3(1024),
-                       (16 + (size_t)(1 << (e->lxg + e->lyg + e->lzg)) + 1) * 4, e->stream,
-                       e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, e->lxg,
-                       e->lyg, e->lzg, sd_mode, g, md);
+                       (16 + (size_t)(1 << (pl.lxg + pl.lyg + pl.lzg)) + 1) * 4, e->stream,
+                       e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, pl.lxg,
+                       pl.lyg, pl.lzg, sd_mode, g, md);
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }
   if (e->has_rod) {
     hipLaunchKernelGGL(swarm::k_rod_run, dim3(e->n_envs), dim3(1024),
-                       swarm::rod_lds_words(e->n, 1 << (e->lxg + e->lyg)) * 4, e->stream,
-                       e->d_derived, e->st, e->rod, n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg,
+                       swarm::rod_lds_words(e->n, 1 << (pl.lxg + pl.lyg)) * 4, e->stream,
+                       e->d_derived, e->st, e->rod, n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg,
                        sd_mode, g, md);
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }
   hipLaunchKernelGGL(swarm::k_global, dim3(e->n_envs), dim3(1024),
-                     global_lds_bytes(e->lxg, e->lyg, e->n, e->params.n_dims), e->stream, e->d_derived, e->st, e->sc,
-                     n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg, sd_mode, g, md);
+                     global_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream, e->d_derived, e->st, e->sc,
+                     n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg, sd_mode, g, md);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
@@ -196,25 +171,26 @@ dim3 per_colloid_grid(const swarm_engine* e) {
 // of 2-D envs above 4096 colloids (launch_build; the deferred build's sort is
 // always the one-workgroup k_build_sort, the stage the fused launches carry).
 int launch_sort(swarm_engine* e, hipStream_t stream, bool chip) {
+  const swarm::EnginePlan& pl = e->plan;
   if (e->params.n_dims == 3) {
     swarm_select::sort_chunk(e->n, [&](auto ch) {
       hipLaunchKernelGGL(swarm::k_build_sort3<ch>, dim3(e->n_envs), dim3(1024), sort_lds_bytes(e),
-                         stream, e->st, e->sc, e->lxb, e->lyb, e->lzb);
+                         stream, e->st, e->sc, pl.lxb, pl.lyb, pl.lzb);
     });
   } else if (chip) {
     hipLaunchKernelGGL(swarm::k_sort_count, per_colloid_grid(e), dim3(256), 0, stream, e->st,
-                       e->sc, e->lxb, e->lyb);
+                       e->sc, pl.lxb, pl.lyb);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(swarm::k_sort_scan, dim3(e->n_envs), dim3(1024),
-                       (size_t)(16 + (1 << (e->lxb + e->lyb)) + 1) * 4, stream, e->sc, e->lxb,
-                       e->lyb);
+                       (size_t)(16 + (1 << (pl.lxb + pl.lyb)) + 1) * 4, stream, e->sc, pl.lxb,
+                       pl.lyb);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(swarm::k_sort_scatter, per_colloid_grid(e), dim3(256), 0, stream, e->st,
-                       e->sc, e->lxb, e->lyb);
+                       e->sc, pl.lxb, pl.lyb);
   } else {
     swarm_select::sort_chunk(e->n, [&](auto ch) {
       hipLaunchKernelGGL(swarm::k_build_sort<ch>, dim3(e->n_envs), dim3(1024), sort_lds_bytes(e),
-                         stream, e->st, e->sc, e->lxb, e->lyb);
+                         stream, e->st, e->sc, pl.lxb, pl.lyb);
     });
   }
   HIP_TRY(hipGetLastError());
@@ -223,13 +199,14 @@ int launch_sort(swarm_engine* e, hipStream_t stream, bool chip) {
 
 // Stage 2, the pair search over the sorted cells (cluster path).
 int launch_pairs(swarm_engine* e, hipStream_t stream) {
+  const swarm::EnginePlan& pl = e->plan;
   if (e->params.n_dims == 3) {
     hipLaunchKernelGGL(swarm::k_build_pairs3, per_colloid_grid(e), dim3(256), 0, stream,
-                       e->d_derived, e->st, e->sc, e->lxb, e->lyb, e->lzb);
+                       e->d_derived, e->st, e->sc, pl.lxb, pl.lyb, pl.lzb);
   } else {
     bools([&](auto local) {
       hipLaunchKernelGGL(swarm::k_build_pairs<local>, per_colloid_grid(e), dim3(256), 0, stream,
-                         e->d_derived, e->st, e->sc, e->lxb, e->lyb);
+                         e->d_derived, e->st, e->sc, pl.lxb, pl.lyb);
     }, e->sc.local_uf != 0);
   }
   HIP_TRY(hipGetLastError());
@@ -238,18 +215,20 @@ int launch_pairs(swarm_engine* e, hipStream_t stream) {
 
 // Stage 2 of the neighbour-list path: Verlet lists, no clusters.
 int launch_nlist_build(swarm_engine* e, hipStream_t stream) {
+  const swarm::EnginePlan& pl = e->plan;
   if (e->params.n_dims == 3)
     hipLaunchKernelGGL(swarm::k_build_nlist3, per_colloid_grid(e), dim3(256), 0, stream,
-                       e->d_derived, e->st, e->sc, e->lxb, e->lyb, e->lzb);
+                       e->d_derived, e->st, e->sc, pl.lxb, pl.lyb, pl.lzb);
   else
     hipLaunchKernelGGL(swarm::k_build_nlist2, per_colloid_grid(e), dim3(256), 0, stream,
-                       e->d_derived, e->st, e->sc, e->lxb, e->lyb);
+                       e->d_derived, e->st, e->sc, pl.lxb, pl.lyb);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
 
 // Stage 3, clusters from the pair list.
 int launch_cluster_build(swarm_engine* e, hipStream_t stream) {
+  const swarm::EnginePlan& pl = e->plan;
   // 2-D: the pair search left block-local union-find roots and a cross list
   // (build_pairs_body); 3-D (k_build_pairs3): the whole pair list is unioned
   const bool local = e->params.n_dims == 2 && e->sc.local_uf;
@@ -268,10 +247,10 @@ int launch_cluster_build(swarm_engine* e, hipStream_t stream) {
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(swarm::k_mwb_pairs, dim3((unsigned)((e->sc.wmax + 3) / 4), e->n_envs),
                        dim3(256), 0, stream, e->st, e->sc);
-  } else if (e->big_build && !local && swarm::build_lds_words_packed(e->n) * 4 <= kMaxLds) {
+  } else if (pl.big_build && !local && swarm::build_lds_words_packed(e->n) * 4 <= kMaxLds) {
     hipLaunchKernelGGL(swarm::k_cluster_build_packed, dim3(e->n_envs), dim3(1024),
                        swarm::build_lds_words_packed(e->n) * 4, stream, e->st, e->sc);
-  } else if (e->big_build) {  // (2-D envs with the local pair search took k_mwb_*)
+  } else if (pl.big_build) {  // (2-D envs with the local pair search took k_mwb_*)
     hipLaunchKernelGGL((swarm::k_cluster_build<true, false>), dim3(e->n_envs), dim3(1024),
                        swarm::build_lds_words_big(e->n) * 4, stream, e->st, e->sc);
   } else {
@@ -286,15 +265,16 @@ int launch_cluster_build(swarm_engine* e, hipStream_t stream) {
 
 // Cluster build of the next window.
 int launch_build(swarm_engine* e, hipStream_t stream) {
-  if (e->env_build) {
+  const swarm::EnginePlan& pl = e->plan;
+  if (pl.env_build) {
     hipLaunchKernelGGL(swarm::k_build_env, dim3(e->n_envs), dim3(1024),
                        build_lds_bytes(e->n, e->sc.pair_cap), stream, e->d_derived, e->st, e->sc,
-                       e->lxb, e->lyb);
+                       pl.lxb, pl.lyb);
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }
-  if (const int rc = launch_sort(e, stream, e->chip_sort)) return rc;
-  if (e->nlist_path) return launch_nlist_build(e, stream);
+  if (const int rc = launch_sort(e, stream, pl.chip_sort)) return rc;
+  if (pl.nlist_path) return launch_nlist_build(e, stream);
   if (const int rc = launch_pairs(e, stream)) return rc;
   return launch_cluster_build(e, stream);
 }
@@ -340,34 +320,35 @@ XcdGrid xcd_grid(int E, int bpe, long flat) {
 constexpr int kMaxStamps = 512;  // captured run nodes with launch stamps
 
 int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullptr) {
+  const swarm::EnginePlan& pl = e->plan;
   const long waves = (long)e->n_envs * e->sc.wmax;
   const bool multi = e->params.n_species > 1;
   const bool walls = e->derived.n_walls != 0;
   const bool pot = e->derived.pot.phi != nullptr;  // swarm_engine_set_potential_field
-  if (e->wide_run) {
+  if (pl.wide_run) {
     // dynamic LDS beyond half a CU's keeps one block (run_wpb run waves) per CU
-    const int R = e->run_wpb;
+    const int R = pl.run_wpb;
     // l1_pairs: the next window's candidate lists built beside the run
     const int ncb = e->sc.l1_pairs ? e->n_envs * ((e->n + 1023) / 1024) : 0;
-    const dim3 grid((unsigned)(e->noise_blocks + ncb + (waves + R - 1) / R));
+    const dim3 grid((unsigned)(pl.noise_blocks + ncb + (waves + R - 1) / R));
     // one block per CU; with rotation helpers (run_wpb <= 2, round 6) their
     // director tables in the dynamic LDS
-    const int helpers = e->rot_helper && R <= 2 ? 1 : 0;
+    const int helpers = pl.rot_helper && R <= 2 ? 1 : 0;
     const size_t lds = helpers ? std::max<size_t>(96 * 1024, R * swarm::helper_lds_bytes())
                                : 96 * 1024;
     bools([&](auto kMulti, auto kWalls, auto kPot) {
       hipLaunchKernelGGL((swarm::k_cluster_run_wide<kMulti, kWalls, kPot>), grid, dim3(1024), lds,
                          e->stream, e->d_derived, e->st, e->sc, e->n_envs, n_steps, e->d_step,
-                         e->d_noise, e->noise_blocks, R, ncb, e->lxb, e->lyb, tstamp, helpers);
+                         e->d_noise, pl.noise_blocks, R, ncb, pl.lxb, pl.lyb, tstamp, helpers);
     }, multi, walls, pot);
-    e->next_table_ready = e->noise_blocks > 0;
+    e->next_table_ready = pl.noise_blocks > 0;
   } else {
     const XcdGrid xg = xcd_grid(e->n_envs, (e->sc.wmax + 3) / 4, (waves + 3) / 4);
     bools([&](auto kTable, auto kMulti, auto kWalls, auto kPot) {
       hipLaunchKernelGGL((swarm::k_cluster_run<kMulti, kTable, kWalls, kPot>), dim3(xg.blocks),
                          dim3(256), 0, e->stream, e->d_derived, e->st, e->sc, e->n_envs, n_steps,
                          e->d_step, e->d_noise, xg.bpe, tstamp);
-    }, e->noise_table, multi, walls, pot);
+    }, pl.noise_table, multi, walls, pot);
     e->next_table_ready = false;
   }
   HIP_TRY(hipGetLastError());
@@ -379,18 +360,20 @@ int launch_run(swarm_engine* e, int n_steps, unsigned long long* tstamp = nullpt
 // global memory: every 2-D build leaves it there (k_build_env too), on the
 // build grid.  after_nlist: the window ran on the neighbour-list path.
 int launch_check(swarm_engine* e, int n_steps, bool after_nlist = false) {
+  const swarm::EnginePlan& pl = e->plan;
   hipLaunchKernelGGL(swarm::k_check, dim3(e->n_envs), dim3(1024),
-                     check_lds_bytes(e->lxg, e->lyg, e->n, e->params.n_dims), e->stream,
-                     e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg,
-                     after_nlist ? 1 : 0, e->lxb, e->lyb);
+                     check_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream,
+                     e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg,
+                     after_nlist ? 1 : 0, pl.lxb, pl.lyb);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
 
 int launch_check3(swarm_engine* e, int n_steps, bool after_nlist) {
+  const swarm::EnginePlan& pl = e->plan;
   hipLaunchKernelGGL(swarm::k_check3, dim3(e->n_envs), dim3(1024), check3_lds_bytes(e), e->stream,
-                     e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, e->lxg, e->lyg,
-                     e->lzg, after_nlist ? 1 : 0);
+                     e->d_derived, e->st, e->sc, n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg,
+                     pl.lzg, after_nlist ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
@@ -437,16 +420,17 @@ int launch_nlist_steps(swarm_engine* e, int n_steps) {
 // the call's last window.
 int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_ready,
                   bool may_defer = false) {
+  const swarm::EnginePlan& pl = e->plan;
   if (!use_prebuilt) {
     const int rc = launch_build(e, e->stream);
     if (rc) return rc;
   }
-  if (e->noise_table && !e->next_table_ready && n_steps > noise_ready) {
+  if (pl.noise_table && !e->next_table_ready && n_steps > noise_ready) {
     const int rc = launch_noise(e, e->stream, n_steps);
     if (rc) return rc;
   }
   const bool three_d = e->params.n_dims == 3;
-  if (e->nlist_path) {
+  if (pl.nlist_path) {
     if (const int rc = launch_nlist_steps(e, n_steps)) return rc;
     return three_d ? launch_check3(e, n_steps, true) : launch_check(e, n_steps, true);
   }
@@ -493,7 +477,7 @@ int launch_window(swarm_engine* e, int n_steps, bool use_prebuilt, int noise_rea
     HIP_TRY(hipEventRecord(ev1, e->stream));
     e->prof_events.emplace_back(ev0, ev1);
   }
-  if (may_defer && e->defer_check && e->wide_run && e->sc.l1_pairs) {
+  if (may_defer && pl.defer_check && pl.wide_run && e->sc.l1_pairs) {
     e->check_pending = true;
     e->check_steps = n_steps;
     return SWARM_OK;
@@ -514,8 +498,9 @@ int run_bd(swarm_engine* e, int n_steps) {
   e->prebuilt_noise_steps = 0;
   while (n_steps > 0) {
     const int w = std::min(n_steps, swarm::kMaxWindow);
-    const int rc = e->cluster_path ? launch_window(e, w, pre, noise_ready, hint && w == n_steps)
-                                   : launch_global(e, w, 0, 0.0f, 0.0f);
+    const int rc = e->plan.cluster_path
+                       ? launch_window(e, w, pre, noise_ready, hint && w == n_steps)
+                       : launch_global(e, w, 0, 0.0f, 0.0f);
     if (rc) return rc;
     pre = false;
     noise_ready = 0;
@@ -532,8 +517,9 @@ int ensure_grid_scratch(swarm_engine* e, int lx, int ly) {
     // the speculative vision grid's saved arguments point into the old buffer
     e->vgrid_ready = false;
     e->spec_ok = false;
-    if (e->d_start) HIP_TRY(hipFree(e->d_start));
-    HIP_TRY(hipMalloc(&e->d_start, need * sizeof(int32_t)));
+    e->start_cap = 0;
+    HIP_TRY(dev_free(e, &e->d_start));
+    HIP_TRY(dev_malloc(e, &e->d_start, need * sizeof(int32_t)));
     e->start_cap = need;
   }
   return SWARM_OK;
@@ -568,6 +554,7 @@ int vision_cone_impl(swarm_engine_t* e, const swarm_vision_params_t* vp, const i
                      int32_t n_agents, const float* radii, const int32_t* types, float* out,
                      bool persistent, const swarm::MlpArgs* pol = nullptr) {
   if (!e || !vp || !agent_idx || !radii || !types || !out) return fail(SWARM_EINVAL, "null argument");
+  const swarm::EnginePlan& pl = e->plan;
   if (const int frc = flush_check(e)) return frc;
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "the vision-cone kernel is 2-D only");
   if (vp->n_cones < 1 || vp->n_cones > SWARM_MAX_CONES || vp->n_types < 1 ||
@@ -621,7 +608,7 @@ int vision_cone_impl(swarm_engine_t* e, const swarm_vision_params_t* vp, const i
     const size_t lds = l1_launch_lds(e, std::max(glds, slds));
     swarm_select::sort_chunk(e->n, [&](auto ch) {
       hipLaunchKernelGGL((k_vgrid_sort<ch>), grid, dim3(1024), lds, e->stream, e->st, va, e->sc,
-                         e->lxb, e->lyb, e->d_derived, nfb, e->d_step);
+                         pl.lxb, pl.lyb, e->d_derived, nfb, e->d_step);
     });
     HIP_TRY(hipGetLastError());
     e->ride_stage = l1 ? 3 : 2;
@@ -654,12 +641,12 @@ int vision_cone_impl(swarm_engine_t* e, const swarm_vision_params_t* vp, const i
     if (pol)
       bools([&](auto local) {
         hipLaunchKernelGGL((k_vision_policy_pairs<4, 16, local, 4, 4>), grid, dim3(256), 0,
-                           e->stream, e->st, e->d_derived, va, *pol, npb, e->sc, e->lxb, e->lyb, pbx);
+                           e->stream, e->st, e->d_derived, va, *pol, npb, e->sc, pl.lxb, pl.lyb, pbx);
       }, e->sc.local_uf != 0);
     else
       bools([&](auto local) {
         hipLaunchKernelGGL((k_vision_pairs<4, 16, local>), grid, dim3(256), 0, e->stream, e->st,
-                           e->d_derived, va, npb, e->sc, e->lxb, e->lyb, pbx);
+                           e->d_derived, va, npb, e->sc, pl.lxb, pl.lyb, pbx);
       }, e->sc.local_uf != 0);
     HIP_TRY(hipGetLastError());
     e->ride_stage = 3;
@@ -698,6 +685,7 @@ int vision_cone_impl(swarm_engine_t* e, const swarm_vision_params_t* vp, const i
 // fused k_field_vgrid_sort (stage 1 and the next observable's grid ride
 // along in the reward launch).
 int launch_field(swarm_engine* e, const FieldArgs& f) {
+  const swarm::EnginePlan& pl = e->plan;
   const int total = f.n_agents * e->n_envs;
   // the reward launch of a slice with a deferred build carries stage 1 (and
   // the l1_pairs pair search), and for a persistent vision cone the next
@@ -721,10 +709,10 @@ int launch_field(swarm_engine* e, const FieldArgs& f) {
       // while every workgroup is resident (the other roles wait for its
       // verdict) and the check's LDS (4 KB of it static) fits
       const dim3 cgrid((unsigned)(nfb + (3 + npf) * e->n_envs));
-      const size_t clds = std::max(lds, check_lds_bytes(e->lxg, e->lyg, e->n, e->params.n_dims));
+      const size_t clds = std::max(lds, check_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims));
       with_check = (int)cgrid.x <= e->n_cus && clds + 4096 <= kMaxLds;
       if (with_check) {
-        ck = CheckArgs{e->check_steps, e->d_step, e->d_arrive, e->lxg, e->lyg, e->lxb, e->lyb};
+        ck = CheckArgs{e->check_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg, pl.lxb, pl.lyb};
         grid = cgrid;
         lds = clds;
       } else if (const int rc = flush_check(e)) {
@@ -734,7 +722,7 @@ int launch_field(swarm_engine* e, const FieldArgs& f) {
     swarm_select::sort_chunk(e->n, [&](auto ch) {
       bools([&](auto check) {
         hipLaunchKernelGGL((k_field_vgrid_sort<ch, check>), grid, dim3(1024), lds, e->stream, f,
-                           nfb, e->st, va, e->sc, e->lxb, e->lyb, e->d_derived, npf, e->d_step,
+                           nfb, e->st, va, e->sc, pl.lxb, pl.lyb, e->d_derived, npf, e->d_step,
                            grid_too ? 1 : 0, ck);
       }, with_check);
     });

@@ -37,6 +37,7 @@
 #include "../../include/swarmrl_amd.h"
 #include "swarm_device.cuh"
 #include "swarm_potential.cuh"
+#include "swarm_sizes.h"
 
 // Sub-step schedule of the run kernels (round 6): off-chain work placed in
 // the latency windows of the position exchange and the force-sum round trip.
@@ -62,34 +63,16 @@ constexpr int kRunMinBlocks = 5;
 #define SWARM_POT_MIN_BLOCKS 4
 #endif
 constexpr int kRunMinBlocksPot = SWARM_POT_MIN_BLOCKS;
-constexpr int kMaxWindow = 128;   // sub-steps per cluster window
-constexpr int kPairsPerWave = 256;  // neighbour pairs of one 64-lane wave (4 passes)
-// Clusters wider than a wave ("big" clusters) run in k_check's workgroup, one
-// member per thread: up to kBigMax members and kBigPairs pairs per env.
-constexpr int kBigMax = 1024;
-constexpr int kBigPairs = 4096;
+// (capacities and LDS sizes shared with the host's planning: swarm_sizes.h)
 constexpr int kBigMark = -0x40000000;  // cbase of a big cluster's root
 // multi-workgroup build (k_mwb_*): sc.bmisc layout per env
-constexpr int kBmWords = 256;  // sc.bmisc words per env
 constexpr int kBmMisc = 0;     // [16]: 0 overflow, 1 waves, 2 pair overflow, 3 free lanes,
                                // 4 big members, 6 big pairs, 8 / 9 tickets
 constexpr int kBmClass = 16;   // [68] cluster count per class
 constexpr int kBmWave = 84;    // [68] first wave of a class
 constexpr int kBmFree = 152;   // [68] first free tail lane of a class (singletons)
 constexpr uint32_t kMwbBig = 0x80000000u;  // B of a big cluster's root: kMwbBig | first member
-constexpr int kMaxMovers = 1024;       // listed movers per env (more: exact re-run)
-// Candidate lists of the next window's pair search (latency-bound ride-along
-// builds, see cand_build_body): per particle up to kCandMax partners j > i
-// within r_i + r_j + skin + 2 cand_disp of the window-start positions.
-constexpr int kCandMax = 24;
 
-// Wave slots per env: every cluster packs into one wave, worst case 2 N
-// slots plus per-size-class rounding.  One-pass packing (latency-bound
-// launches, see k_cluster_build) reserves up to 2 s lanes for a cluster of
-// s particles: worst case 4 N.
-__host__ __device__ inline int slots_per_env(int n, bool one_pass = false) {
-  return (one_pass ? 4 : 2) * n + 64 * 66;
-}
 constexpr float kAngInvScale = 683565275.57643158f;  // 2^32 / (2 pi)
 
 // fp32 constants derived from swarm_params_t (same derivation as the oracle).
@@ -202,9 +185,9 @@ __device__ __forceinline__ void save_forces_env(const DevState& st, int e, int w
   for (int i = threadIdx.x; i < st.n; i += blockDim.x) save_forces(st, base + i, wp);
 }
 
-// Device control block (uint64 words): step counter, window counter, and
-// the two noise tables' first step / length (by window parity, see k_noise).
-constexpr int kCtlStep = 0, kCtlWin = 1, kCtlTStep = 2, kCtlTLen = 4, kCtlWords = 8;
+// Device control block (kCtlWords uint64 words): step counter, window counter,
+// and the two noise tables' first step / length (by window parity, see k_noise).
+constexpr int kCtlStep = 0, kCtlWin = 1, kCtlTStep = 2, kCtlTLen = 4;
 
 __device__ __forceinline__ int window_parity(const uint64_t* ctl) {
   return (int)(ctl[kCtlWin] & 1ull);  // written by earlier launches only
@@ -939,18 +922,6 @@ __device__ void block_global_run(const Derived* __restrict__ d, const DevState& 
 __device__ unsigned long long g_global_phase[4];  // cycles: sort, forces+step, steps
 #endif
 
-// LDS words the register-resident global path needs after the cell counts
-// (sorted positions as uint2 + ids), 0 when it does not apply (3-D, or more
-// than kGlobalCH particles per thread of a 1024-thread block).
-constexpr int kGlobalCH = 4;
-__host__ __device__ inline size_t global_lds_extra_words(int n, int dims, int ncell) {
-  const size_t extra = 8 * (size_t)n + 2;
-  // k_check's layout (the larger): 16 + 16 + 1024 + ncell + 1 words first,
-  // and 4 KB of static LDS beside it
-  const bool fits = (16 + 16 + 1024 + (size_t)ncell + 1 + extra) * 4 + 4096 <= 160 * 1024;
-  return dims == 2 && n <= kGlobalCH * 1024 && fits ? extra : 0;
-}
-
 // The global path with the particle state and the per-sub-step cell sort in
 // LDS (up to kGlobalCH particles per thread): same pair_force / bd_step /
 // sd_step sequence and int64 force sums as block_global_run, so the same
@@ -1235,13 +1206,6 @@ __device__ __forceinline__ int wave_class_add(int32_t* ctr, bool pred) {
   if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(ctr, __builtin_popcountll(m));
   base = __shfl(base, leader);
   return base + below;
-}
-
-// LDS words of k_cluster_build: 168 fixed + per-wave pair counters +
-// parent[N] + 3 N (cluster sizes, bases, slots) + the env's pair list.
-__host__ __device__ inline size_t build_lds_words(int n, int pair_cap) {
-  const int wmax = slots_per_env(n, true) / 64;  // either packing
-  return 16 + 16 + 3 * 68 + (size_t)((wmax + 3) & ~3) + 4 * (size_t)n + (size_t)pair_cap;
 }
 
 // Build step 1, one workgroup per env: counting sort into cells of side
@@ -2008,12 +1972,6 @@ __device__ __forceinline__ int free_class(const int32_t* freebase, int r) {
   return v;
 }
 
-// LDS words of the large-N variant: the union-find forest only.
-__host__ __device__ inline size_t build_lds_words_big(int n) {
-  const int wmax = slots_per_env(n, true) / 64;  // either packing
-  return 16 + 16 + 3 * 68 + (size_t)((wmax + 3) & ~3) + (size_t)n;
-}
-
 // Build step 3, one workgroup per env: union-find over the pair list
 // (connected components = clusters), packing of the clusters into 64-lane
 // wave slots that never straddle a wave, per-wave pair lists.  kBig: the
@@ -2376,12 +2334,6 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
     sc.big_n[e] = misc[5];
     sc.big_np[e] = min(misc[6], kBigPairs);
   }
-}
-
-// LDS words of the packed large-N build: two words per particle (N < 65536).
-__host__ __device__ inline size_t build_lds_words_packed(int n) {
-  const int wmax = slots_per_env(n, true) / 64;
-  return 16 + 16 + 3 * 68 + (size_t)((wmax + 3) & ~3) + 2 * (size_t)n;
 }
 
 // The large-N build (same result as cluster_build_env<true, false>) with
@@ -2907,12 +2859,6 @@ __global__ __launch_bounds__(1024) void k_cluster_build(DevState st, Scratch sc)
   cluster_build_env<kBig, !kBig, kLocal>(st, sc, blockIdx.x, smem, sc.gnpairs[blockIdx.x]);
 }
 
-// Words of k_build_env's sort/search region (wave sums, cell ends, sorted
-// x, y, id), which must fit below the pair list of the build's LDS layout.
-__host__ __device__ inline size_t build_env_sort_words(int n, int ncell) {
-  return 16 + (size_t)((ncell + 2) & ~1) + 3 * (size_t)n;
-}
-
 // The whole build of one env in one workgroup, LDS-resident (no global
 // intermediates, one launch): counting sort of the positions into cells of
 // side >= rc_max + skin, the pair search over the sorted LDS copy (every pair
@@ -3119,7 +3065,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // on otherwise idle CUs while it reads this one's.  The control block
 // records each table's first step and length; a run whose window does not
 // match its table draws the normals itself.
-__host__ __device__ inline size_t noise_table_words(size_t M) { return (size_t)kMaxWindow * 3 * M; }
+// (noise_table_words(M), one table's size: swarm_sizes.h)
 // word of normal c of sub-step s of particle gi; the step and component strides
 __host__ __device__ inline size_t noise_index(size_t M, size_t gi, int s, int c) {
   (void)M;
@@ -4124,7 +4070,7 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
 // after an odd window).  Forces, noise and update are block_global_run's
 // (pair_force, bd_step with the step's normals drawn fresh), so the bits are
 // the same.  The 3-D twin is k_build_nlist3 / k_nl_step3.
-constexpr int kNlMax = 48;  // neighbours per colloid (more: the env re-runs)
+// (kNlMax neighbours per colloid; more: the env re-runs)
 
 // Build step 2 (neighbour-list path), grid (ceil(N / 256), E), one thread
 // per cell-sorted entry of k_build_sort: its neighbours into nl[k][gi]

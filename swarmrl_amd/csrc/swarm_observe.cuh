@@ -621,9 +621,7 @@ __device__ __forceinline__ int fused_block(int nfirst) {
 // (swarm::pair_filter_body; ctl: the device control block, whose window
 // counter names this window's build sort).  smem: the launch's dynamic LDS,
 // at least l1_role_lds_bytes() (the fallback cell search's tables).
-constexpr size_t l1_role_lds_bytes() {
-  return (kMaxSpecies * kMaxSpecies + 2 * 1024) * sizeof(int32_t);
-}
+using swarm::l1_role_lds_bytes;
 __device__ __forceinline__ void l1_pairs_role(const Derived* __restrict__ d, const DevState& st,
                                               const Scratch& sc, int lxb, int lyb, int fb, int n_fb,
                                               const uint64_t* ctl, unsigned char* smem) {
