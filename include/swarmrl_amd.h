@@ -256,6 +256,42 @@ typedef struct swarm_rod {
  * n <= 255; at most 4096 particles per env; one rod per engine. */
 int swarm_engine_set_rod(swarm_engine_t *e, const swarm_rod_t *rod);
 
+/* Ellipsoidal colloids (espresso.py:802-832 and 420-436): the aspect ratio
+ * every particle shares (axial over equatorial semi-axis; the species'
+ * radius is the equatorial one) and per species the translational friction
+ * along the director (gamma_par = gamma_translation[2] of the 2-D body
+ * frame, espresso.py:427-449) and across it in the plane (gamma_perp =
+ * gamma_translation[1]).  The rotational friction about lab z stays
+ * swarm_params_t::gamma_r. */
+typedef struct swarm_ellipsoids {
+  double aspect_ratio;
+  double gamma_par[SWARM_MAX_SPECIES];
+  double gamma_perp[SWARM_MAX_SPECIES];
+} swarm_ellipsoids_t;
+
+/* Replaces the gay_berne.set_params calls of _setup_interactions
+ * (espresso.py:802-832: k2 = 1, nu = 1, mu = 2, sig = (r_i + r_j) 2^(-1/6),
+ * eps = wca_epsilon) and the per-axis gamma of part.add (espresso.py:420-436);
+ * call once, before the first swarm_engine_integrate or
+ * swarm_engine_remove_overlap (SWARM_ESTATE afterwards).  With aspect_ratio
+ * != 1 every pair interacts by Gay-Berne, shifted at the cutoff
+ * 2 (r_i + r_j) max(k, 1 / k) (espresso.py:830 for equal radii), and the
+ * per-env cell grid is re-derived for the widest of them; with aspect_ratio
+ * = 1 the pairs stay WCA and only the friction is per axis.  A pair that
+ * penetrates to X = sigma0 / (|r| - sigma + sigma0) >= 1.25 (or
+ * |r| - sigma + sigma0 <= 0) contributes the force and torque at X = 1.25
+ * and is counted, per visit and sub-step, in swarm_engine_wall_violations.
+ * From then on every sub-step and the overlap removal (in which the
+ * Gay-Berne force and torque act too) run in one workgroup per env; the
+ * engine runs no cluster windows and declines swarm_engine_prebuild,
+ * swarm_engine_defer_build, swarm_engine_prebuild_noise and
+ * swarm_engine_hint_defer_check.  SWARM_EINVAL for a rod, walls, a
+ * potential, a non-periodic box, n_dims = 3, aspect_ratio <= 0, a
+ * non-positive friction or a cutoff of half the box or more;
+ * SWARM_ECAPACITY when the env's state does not fit the 160 KB of LDS of one
+ * workgroup (the message states the particle limit). */
+int swarm_engine_set_ellipsoids(swarm_engine_t *e, const swarm_ellipsoids_t *ell);
+
 /* RotateRod's reward on the device (rod_rotation.py:87-219 with
  * compute_torque_partition_on_rod, colloid_utils.py:29-117), all in fp64:
  *   step = wrapped (centre angle - hist_ang[e]) in degrees, pushed into the

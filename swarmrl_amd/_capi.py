@@ -98,6 +98,16 @@ class SwarmRod(ctypes.Structure):
     ]
 
 
+class SwarmEllipsoids(ctypes.Structure):
+    """swarm_ellipsoids_t: the common aspect ratio, per species the friction
+    along and across the director."""
+    _fields_ = [
+        ("aspect_ratio", ctypes.c_double),
+        ("gamma_par", ctypes.c_double * SWARM_MAX_SPECIES),
+        ("gamma_perp", ctypes.c_double * SWARM_MAX_SPECIES),
+    ]
+
+
 class SwarmVisionParams(ctypes.Structure):
     _fields_ = [
         ("vision_range", ctypes.c_float),
@@ -307,6 +317,7 @@ _SIGNATURES = {
     ),
     "swarm_engine_wall_violations": (ctypes.c_int, [_P, _P]),
     "swarm_engine_set_rod": (ctypes.c_int, [_P, ctypes.POINTER(SwarmRod)]),
+    "swarm_engine_set_ellipsoids": (ctypes.c_int, [_P, ctypes.POINTER(SwarmEllipsoids)]),
     "swarm_rod_reward": (
         ctypes.c_int,
         [_P, _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _P],

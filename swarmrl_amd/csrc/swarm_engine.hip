@@ -42,6 +42,7 @@
 #include "swarm_ensemble.cuh"
 #include "swarm_rnd.cuh"
 #include "swarm_rod.cuh"
+#include "swarm_ellipsoid.cuh"
 #include "swarm_observe.cuh"
 #include "swarm_plan.h"
 
@@ -124,8 +125,9 @@ struct swarm_engine {
   int device = 0;
   int n_cus = 0;
   // the cell grids, every path choice and the buffer sizes (swarm_plan.h).
-  // Nothing writes it after swarm_engine_create but swarm_engine_set_rod,
-  // which takes the engine off the cluster path for good.
+  // Nothing writes it after swarm_engine_create but swarm_engine_set_rod and
+  // swarm_engine_set_ellipsoids, which take the engine off the cluster path
+  // for good (the latter also widens the global-path grid).
   swarm::EnginePlan plan;
   DevState st{};
   Scratch sc{};
@@ -206,6 +208,12 @@ struct swarm_engine {
   // swarm_engine_set_rod: every sub-step runs on k_rod_run (swarm_rod.cuh)
   bool has_rod = false;
   swarm::RodArgs rod{};
+  // swarm_engine_set_ellipsoids: every sub-step runs on k_ellipsoid_run
+  // (swarm_ellipsoid.cuh); ell_gb: aspect ratio != 1 (Gay-Berne pairs)
+  bool has_ell = false, ell_gb = false;
+  swarm::EllArgs* d_ell = nullptr;
+  // a sub-step or an overlap-removal step has run
+  bool stepped = false;
   // swarm_engine_set_potential_field: the field's device copy (derived.pot.phi
   // points at it while a field is set) and its capacity in values
   float* d_pot = nullptr;
@@ -636,6 +644,7 @@ int swarm_engine_remove_overlap(swarm_engine_t* e, int32_t n_steps, double gamma
   e->ride_stage = 0;
   e->prebuilt_noise_steps = 0;
   if (n_steps <= 0) return SWARM_OK;
+  e->stepped = true;
   return launch_global(e, n_steps, 1, (float)gamma, (float)max_disp);
 }
 
@@ -644,6 +653,7 @@ int swarm_engine_integrate(swarm_engine_t* e, int32_t n_steps) {
   if (const int frc = flush_check(e)) return frc;
   if (n_steps < 0) return fail(SWARM_EINVAL, "n_steps must be >= 0");
   if (n_steps == 0) return SWARM_OK;
+  e->stepped = true;
   return run_bd(e, n_steps);
 }
 
@@ -1424,6 +1434,8 @@ int swarm_engine_set_walls(swarm_engine_t* e, const swarm_wall_t* walls, int32_t
   if (n_walls < 0 || n_walls > SWARM_MAX_WALLS) return fail(SWARM_ECAPACITY, "0 <= n_walls <= 16");
   if (n_walls > 0 && !walls) return fail(SWARM_EINVAL, "null walls");
   if (n_walls > 0 && e->has_rod) return fail(SWARM_EINVAL, "walls with a rod are not supported");
+  if (n_walls > 0 && e->has_ell)
+    return fail(SWARM_EINVAL, "walls with ellipsoids are not supported");
   Derived& d = e->derived;
   d.n_walls = n_walls;
   for (int k = 0; k < n_walls; ++k) {
@@ -1469,6 +1481,7 @@ int swarm_engine_set_potential_field(swarm_engine_t* e, const float* phi, int32_
   } else {
     if (!spacing) return fail(SWARM_EINVAL, "null spacing");
     if (e->has_rod) return fail(SWARM_EINVAL, "a potential with a rod is not supported");
+    if (e->has_ell) return fail(SWARM_EINVAL, "a potential with ellipsoids is not supported");
     const int32_t n[3] = {nx, ny, nz};
     for (int a = 0; a < 3; ++a)
       if (n[a] < 1) return fail(SWARM_EINVAL, "grid counts must be positive");
@@ -1553,6 +1566,7 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   if (!e || !rod) return fail(SWARM_EINVAL, "null argument");
   if (const int frc = flush_check(e)) return frc;
   if (e->has_rod) return fail(SWARM_EINVAL, "the engine already has a rod");
+  if (e->has_ell) return fail(SWARM_EINVAL, "a rod with ellipsoids is not supported");
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "Rod can only be added in 2d");
   if (!e->params.periodic) return fail(SWARM_EINVAL, "a rod needs a periodic box");
   if (e->derived.n_walls) return fail(SWARM_EINVAL, "a rod with walls is not supported");
@@ -1593,6 +1607,101 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   e->ride_stage = 0;
   if (const int rc = launch_rod_snap(e)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+// Ellipsoids (espresso.py:802-832, 420-436): the per-engine constants of
+// k_ellipsoid_run (swarm_ellipsoid.cuh), in fp64 and rounded once.
+int swarm_engine_set_ellipsoids(swarm_engine_t* e, const swarm_ellipsoids_t* ell) {
+  if (!e || !ell) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (e->stepped)
+    return fail(SWARM_ESTATE, "ellipsoids must be set before the first integrate or overlap removal");
+  if (e->has_ell) return fail(SWARM_EINVAL, "the engine already has ellipsoids");
+  const swarm_params_t& p = e->params;
+  if (p.n_dims != 2) return fail(SWARM_EINVAL, "ellipsoids are 2-D only");
+  if (!p.periodic) return fail(SWARM_EINVAL, "ellipsoids need a periodic box");
+  if (e->has_rod) return fail(SWARM_EINVAL, "ellipsoids with a rod are not supported");
+  if (e->derived.n_walls) return fail(SWARM_EINVAL, "ellipsoids with walls are not supported");
+  if (e->derived.pot.phi) return fail(SWARM_EINVAL, "ellipsoids with a potential are not supported");
+  const double k = ell->aspect_ratio;
+  if (!(k > 0.0) || !std::isfinite(k)) return fail(SWARM_EINVAL, "aspect_ratio must be positive");
+  for (int s = 0; s < p.n_species; ++s)
+    if (!(ell->gamma_par[s] > 0.0) || !(ell->gamma_perp[s] > 0.0) ||
+        !std::isfinite(ell->gamma_par[s]) || !std::isfinite(ell->gamma_perp[s]))
+      return fail(SWARM_EINVAL, "the frictions along and across the director must be positive");
+  const bool gb = k != 1.0;
+  const double wide = 2.0 * std::max(k, 1.0 / k);
+  int lx = e->plan.lxg, ly = e->plan.lyg;
+  if (gb) {
+    // Gay-Berne cutoff 2 (r_i + r_j) max(k, 1 / k) against WCA's r_i + r_j:
+    // the grid of the widest pair (swarm::max_cutoff)
+    const double rc = wide * swarm::max_cutoff(p);
+    if (!(rc < 0.5 * std::min(p.box[0], p.box[1])))
+      return fail(SWARM_EINVAL, "the Gay-Berne cutoff must be below half the box");
+    cell_grid(p, e->n, rc, &lx, &ly);
+  }
+  const size_t fixed = swarm::kEllStaticLds;
+  auto fits = [&](int n, int gx, int gy) {
+    return swarm::ell_lds_words(n, 1 << (gx + gy)) * 4 + fixed <= kMaxLds;
+  };
+  if (!fits(e->n, lx, ly)) {
+    // 40 bytes of state per particle beside the cell counts and the pair
+    // tables: the most this box and cutoff admit
+    int limit = e->n, gx = lx, gy = ly;
+    while (limit > 1 && !fits(limit, gx, gy)) {
+      --limit;
+      cell_grid(p, limit, gb ? wide * swarm::max_cutoff(p) : swarm::max_cutoff(p), &gx, &gy);
+    }
+    return fail(SWARM_ECAPACITY, "an engine with ellipsoids holds at most " +
+                                     std::to_string(limit) +
+                                     " particles per env in this box (the 160 KB of LDS of one"
+                                     " workgroup)");
+  }
+  swarm::EllArgs a{};
+  const double chi = (k * k - 1.0) / (k * k + 1.0);
+  a.chi = (float)chi;
+  a.hchi = (float)(0.5 * chi);
+  a.chi2 = (float)(chi * chi);
+  a.eps4 = (float)(4.0 * p.wca_epsilon);
+  const double kT = p.kT, dt = p.time_step;
+  for (int s = 0; s < p.n_species; ++s) {
+    const double ga = ell->gamma_par[s], gq = ell->gamma_perp[s];
+    a.mob_par[s] = (float)(dt / ga);
+    a.mob_perp[s] = (float)(dt / gq);
+    a.sig_par[s] = (float)std::sqrt(2.0 * kT * dt / ga);
+    a.sig_perp[s] = (float)std::sqrt(2.0 * kT * dt / gq);
+    a.inv_gpar[s] = (float)(1.0 / ga);
+    a.inv_gperp[s] = (float)(1.0 / gq);
+    for (int t = 0; t < p.n_species; ++t) {
+      const double rs = p.radius[s] + p.radius[t];
+      const double s0 = rs * std::pow(2.0, -1.0 / 6.0), rc = wide * rs;
+      const int pk = s * swarm::kMaxSpecies + t;
+      a.sig0[pk] = (float)s0;
+      a.isig0[pk] = s0 > 0.0 ? (float)(1.0 / s0) : 0.0f;
+      a.rcut[pk] = (float)rc;
+      a.rcut2[pk] = (float)(rc * rc);
+    }
+  }
+  HIP_TRY(dev_malloc(e, &e->d_ell, sizeof(swarm::EllArgs)));
+  HIP_TRY(hipMemcpyAsync(e->d_ell, &a, sizeof(a), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // (a is a local)
+  e->has_ell = true;
+  e->ell_gb = gb;
+  // as swarm_engine_set_rod: no cluster windows, and none of what prepares
+  // or checks them
+  e->plan.lxg = lx;
+  e->plan.lyg = ly;
+  e->plan.cluster_path = false;
+  e->plan.nlist_path = false;
+  e->plan.noise_table = false;
+  e->plan.wide_run = false;
+  e->plan.env_build = false;
+  e->plan.defer_check = false;
+  e->defer_hint = false;
+  e->prebuilt = false;
+  e->prebuilt_noise_steps = 0;
+  e->ride_stage = 0;
   return SWARM_OK;
 }
 

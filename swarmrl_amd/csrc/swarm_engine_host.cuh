@@ -107,11 +107,13 @@ void allow_engine_lds(int device) {
     swarm_select::each_sort_chunk([&](auto ch) { allow(&k_field_vgrid_sort<ch, check>); });
   });
   allow(&k_policy_cbuild<4, 4, 4>);
+  // (last: every kernel above keeps its place in the code object)
+  swarm_select::each_bools<1>([&](auto gb) { allow(&swarm::k_ellipsoid_run<gb>); });
   (void)hipGetLastError();
   done.push_back(device);
 }
 
-// ---- the global path, the rod, the noise table
+// ---- the global path, the rod, the ellipsoids, the noise table
 
 int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) {
   const swarm::EnginePlan& pl = e->plan;
@@ -128,6 +130,16 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
                        swarm::rod_lds_words(e->n, 1 << (pl.lxg + pl.lyg)) * 4, e->stream,
                        e->d_derived, e->st, e->rod, n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg,
                        sd_mode, g, md);
+    HIP_TRY(hipGetLastError());
+    return SWARM_OK;
+  }
+  if (e->has_ell) {
+    bools([&](auto gb) {
+      hipLaunchKernelGGL(swarm::k_ellipsoid_run<gb>, dim3(e->n_envs), dim3(1024),
+                         swarm::ell_lds_words(e->n, 1 << (pl.lxg + pl.lyg)) * 4, e->stream,
+                         e->d_derived, e->st, e->d_ell, n_steps, e->d_step, e->d_arrive, pl.lxg,
+                         pl.lyg, sd_mode, g, md);
+    }, e->ell_gb);
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }

@@ -9,9 +9,9 @@ holder) mirrors the reference line by line; the physics that ESPResSo did
 library through the C ABI of include/swarmrl_amd.h.  There is no CPU
 fallback: without a HIP device the engine raises.
 
-Scope of this build: 2-D, periodic box, isotropic spheres
-(WCA), Brownian thermostat, one rigid rod (add_rod).  Gay-Berne, LB and the
-Langevin integrator raise NotImplementedError.
+Scope of this build: 2-D, periodic box, spheres (WCA) or
+ellipsoids (Gay-Berne, per-axis friction), Brownian thermostat, one rigid rod
+(add_rod).  LB and the Langevin integrator raise NotImplementedError.
 """
 
 from __future__ import annotations
@@ -108,6 +108,32 @@ def _calc_friction_coefficients(dyn_visc: float, radius: float):
     particle_gamma_translation = 6 * np.pi * dyn_visc * radius
     particle_gamma_rotation = 8 * np.pi * dyn_visc * radius**3
     return particle_gamma_translation, particle_gamma_rotation
+
+
+class _SpeciesKey(tuple):
+    """A species' (radius, gamma_translation, gamma_rotation, mass, rinertia)
+    as before, and beside it the translational friction across the director
+    (2-D per-axis friction; gamma_translation is then the one along it)."""
+
+    def __new__(cls, values, gamma_perp=None):
+        self = super().__new__(cls, values)
+        self.gamma_perp = float(values[1] if gamma_perp is None else gamma_perp)
+        return self
+
+    def _perp_of(self, other):
+        return getattr(other, "gamma_perp", other[1] if len(other) > 1 else None)
+
+    def __eq__(self, other):
+        if not isinstance(other, tuple):
+            return NotImplemented
+        return tuple.__eq__(self, other) and self.gamma_perp == self._perp_of(other)
+
+    def __ne__(self, other):
+        eq = self.__eq__(other)
+        return eq if eq is NotImplemented else not eq
+
+    def __hash__(self):
+        return hash((tuple(self), self.gamma_perp))
 
 
 def _vector_from_angles(theta, phi):
@@ -386,9 +412,12 @@ class SwarmEngine(Engine):
                     f" {self.colloid_radius_register[type_colloid]['radius']}. Choose a"
                     " new combination"
                 )
-        if aspect_ratio != 1.0:
+        aspect_ratio = float(aspect_ratio)
+        if not aspect_ratio > 0.0:
+            raise ValueError(f"aspect_ratio must be positive. You gave {aspect_ratio}")
+        if aspect_ratio != 1.0 and self.n_dims == 3:
             raise NotImplementedError(
-                "aspect_ratio != 1 (Gay-Berne) is not implemented in this build"
+                "aspect_ratio != 1 (Gay-Berne) is implemented for 2d engines only"
             )
         gt_sphere, gr_sphere = _calc_friction_coefficients(
             self.params.fluid_dyn_viscosity.m_as("sim_dyn_viscosity"), radius_simunits
@@ -403,8 +432,21 @@ class SwarmEngine(Engine):
             gamma_rotation = gamma_rotation.m_as("sim_torque/sim_angular_velocity")
         gamma_translation = np.atleast_1d(np.asarray(gamma_translation, dtype=float))
         gamma_rotation = np.atleast_1d(np.asarray(gamma_rotation, dtype=float))
-        if np.ptp(gamma_translation) != 0.0 or np.ptp(gamma_rotation) != 0.0:
-            raise NotImplementedError("anisotropic friction is not implemented in this build")
+        for name, gam in (("gamma_translation", gamma_translation),
+                          ("gamma_rotation", gamma_rotation)):
+            if gam.shape not in ((1,), (3,)) or not np.all(gam > 0.0):
+                raise ValueError(f"{name} must be a positive scalar or 3-vector. You gave {gam}")
+        per_axis = np.ptp(gamma_translation) != 0.0 or np.ptp(gamma_rotation) != 0.0
+        if per_axis and self.n_dims == 3:
+            raise NotImplementedError(
+                "per-axis friction is implemented for 2d engines only")
+        # the 2-D body frame (espresso.py:427-449): body z the director, body
+        # y the in-plane normal, body x lab z; the other components are unused
+        three = gamma_translation.shape == (3,)
+        gamma_par = float(gamma_translation[2 if three else 0])
+        gamma_perp = float(gamma_translation[1 if three else 0])
+        if aspect_ratio != 1.0 or gamma_par != gamma_perp:
+            self._validate_ellipsoids(adding=True)
 
         if self.params.thermostat_type == "langevin":
             if mass is None:
@@ -424,12 +466,9 @@ class SwarmEngine(Engine):
         rin = np.atleast_1d(rinertia.m_as("sim_rinertia"))
         # 2-D rotation is about lab z = body x after _rotate_colloid_to_2d
         rin_z = float(rin[0])
-        key = (
-            float(radius_simunits),
-            float(gamma_translation[0]),
-            float(gamma_rotation[0]),
-            mass_s,
-            rin_z,
+        key = _SpeciesKey(
+            (float(radius_simunits), gamma_par, float(gamma_rotation[0]), mass_s, rin_z),
+            gamma_perp,
         )
         return radius_simunits, key
 
@@ -445,7 +484,19 @@ class SwarmEngine(Engine):
         mass: Quantity = None,
         rinertia: Quantity = None,
     ):
-        """Add one colloid at a point (espresso.py:307-457); same point in every env."""
+        """Add one colloid at a point (espresso.py:307-457); same point in every env.
+
+        aspect_ratio: axial over equatorial semi-axis of a spheroid whose
+        equatorial radius is radius_colloid; != 1 makes every pair interact by
+        Gay-Berne (2-D engines, one aspect ratio per system).
+        gamma_translation, gamma_rotation: a scalar or a 3-vector in body-frame
+        order.  In 2-D the body frame is the reference's (espresso.py:427-449):
+        body z is the director, body y the in-plane normal, body x lab z, so
+        translation along the director uses gamma_translation[2], across it
+        gamma_translation[1], and the rotation about lab z gamma_rotation[0];
+        gamma_translation[0], gamma_rotation[1] and gamma_rotation[2] are
+        accepted and unused.  Ellipsoids and per-axis friction are not
+        implemented in 3-D nor together with an external potential."""
         self._check_already_initialised()
         if init_position is None:
             init_position = 0.5 * self.params.box_length
@@ -497,7 +548,8 @@ class SwarmEngine(Engine):
         """
         Random placement in a disc (espresso.py:459-544).  Per colloid the
         generator draws r, theta, then the director angle (espresso.py:95-96,
-        532); env e uses its own generator.
+        532); env e uses its own generator.  aspect_ratio and the frictions:
+        as add_colloid_on_point.
         """
         self._check_already_initialised()
         if random_placement_center is None:
@@ -665,6 +717,45 @@ class SwarmEngine(Engine):
                 f"per env. You have {total}"
             )
 
+    def _has_ellipsoids(self) -> bool:
+        """Whether the engine needs the ellipsoid path: an aspect ratio other
+        than 1 or a species whose friction differs along and across the
+        director."""
+        if any(d["aspect_ratio"] != 1.0 for d in self.colloid_radius_register.values()):
+            return True
+        return any(getattr(k, "gamma_perp", k[1]) != k[1] for k in self._species_keys)
+
+    def _validate_ellipsoids(self, adding=False, potential=False):
+        """What the ellipsoid path cannot run: refused when such a colloid is
+        added, when a potential is added beside one, and again at the first
+        integrate.  adding: an ellipsoid (or a colloid with per-axis friction)
+        is about to be added; potential: an external potential is."""
+        if not (adding or self._has_ellipsoids()):
+            return
+        if self.n_dims != 2:
+            raise NotImplementedError("ellipsoids are implemented for 2d engines only")
+        if self.params.thermostat_type != "brownian":
+            raise NotImplementedError(
+                "ellipsoids are implemented for the brownian thermostat only")
+        # k_ellipsoid_run does not read the field
+        if self._potential is not None or potential:
+            raise NotImplementedError(
+                "ellipsoids or per-axis friction together with an external potential are"
+                " not implemented")
+        if adding:
+            return
+        aspect_ratios = [d["aspect_ratio"] for d in self.colloid_radius_register.values()]
+        if len(np.unique(aspect_ratios)) > 1:
+            raise ValueError("All particles in the system must have the same aspect ratio.")
+        # (aspect ratio 1 with per-axis friction: walls and the rod pass the check above)
+        if self._walls or self._rod is not None:
+            raise NotImplementedError(
+                "per-axis friction together with walls or a rod is not implemented")
+        if not self.params.periodic:
+            raise NotImplementedError("ellipsoids in a non-periodic box are not implemented")
+        # (the particle limit of the kernel's LDS depends on the box and the
+        # cutoff: swarm_engine_set_ellipsoids states it)
+
     def add_const_force_to_colloids(self, force: Quantity, type: int):
         """Constant external force on every colloid of a type (espresso.py:834-851).
         The force is kept per type and laid out per colloid when it is handed
@@ -816,6 +907,7 @@ class SwarmEngine(Engine):
         if pot.size * (4 if self.n_dims == 2 else 1) > 2**31 - 1:
             raise ValueError("the potential grid is too large")
         self._validate_rod(potential=True)
+        self._validate_ellipsoids(potential=True)
         if self._potential is not None:
             old = self._potential
             if old["phi"].shape != pot.shape or not np.array_equal(old["h"], agrids):
@@ -923,6 +1015,14 @@ class SwarmEngine(Engine):
             rod.first, rod.n = self._rod["first"], self._rod["n"]
             rod.delta, rod.fixed = self._rod["delta"], 1 if self._rod["fixed"] else 0
             self._native.call("swarm_engine_set_rod", ctypes.byref(rod))
+
+        if self._has_ellipsoids():  # espresso.py:802-832, 420-436
+            ell = _capi.SwarmEllipsoids()
+            ell.aspect_ratio = float(aspect_ratios[0])
+            for s, key in enumerate(self._species_keys):
+                ell.gamma_par[s] = key[1]
+                ell.gamma_perp[s] = getattr(key, "gamma_perp", key[1])
+            self._native.call("swarm_engine_set_ellipsoids", ctypes.byref(ell))
 
         self._types_host = np.asarray(self._types_list, dtype=np.int32)
         self._types_device = torch.as_tensor(self._types_host, device=self.device)
@@ -1266,6 +1366,7 @@ class SwarmEngine(Engine):
             self.slice_idx = 0
             self.step_idx = 0
             self._validate_rod()
+            self._validate_ellipsoids()
             self._setup_interactions()
             self._remove_overlap()
             self._init_h5_output()
