@@ -13,7 +13,7 @@
 // A torque per pair and a step in the body frame: neither fits the cluster
 // windows, so an engine with ellipsoids (swarm_engine_set_ellipsoids) runs
 // every sub-step and the overlap removal on k_ellipsoid_run, one workgroup
-// per env, modelled on block_global_run_lds / k_rod_run: state and the
+// per env, a path of block_env_run (swarm_env_block.cuh): state and the
 // per-sub-step counting sort in LDS, every particle walks the 3 x 3 cells,
 // forces and the z-torque summed in int64 at 2^-24 (independent of visiting
 // order).  kGB = false (aspect ratio 1, per-axis friction): pair_force (WCA)
@@ -52,13 +52,6 @@ struct EllPairTables {
 // Static LDS of k_ellipsoid_run<true>: both pair tables and 256 bytes of the
 // helpers' own (the build's resource report states the total, 6400).
 constexpr size_t kEllStaticLds = sizeof(PairTables) + sizeof(EllPairTables) + 256;
-
-// Dynamic LDS of k_ellipsoid_run in 4-byte words: wave sums, cell counts,
-// (8-byte aligned) the sorted positions and directors (uint2, float2), the
-// sorted ids and the particle state (q, img, ang).
-__host__ __device__ inline size_t ell_lds_words(int n, int ncell) {
-  return 16 + (size_t)ncell + 1 + 1 + 10 * (size_t)n;
-}
 
 // Gay-Berne force and z-torque on i from j (r = x_j - x_i, u_i = (ci, si),
 // u_j = (cj, sj)) with k2 = 1, nu = 1, mu = 2, shifted at the cutoff, added in
@@ -172,142 +165,48 @@ __device__ __forceinline__ void ell_step(const EllArgs* __restrict__ ea, int sp,
   }
 }
 
-// All sub-steps (or steepest-descent steps) of env e by one workgroup.
+// block_env_run for ellipsoids: the directors travel with the sorted
+// positions, the pair term is Gay-Berne's (kGB) with its torque, and the step
+// is the body frame's.
 template <bool kGB>
-__device__ __forceinline__ void block_ellipsoid_run(
-    const Derived* __restrict__ d, const DevState& st, const EllArgs* __restrict__ ea, int e,
-    int n_steps, uint64_t step0, int lx, int ly, bool sd_mode, float g, float md, int32_t* cnt,
-    int32_t* wave_sums, int32_t* lsq, const PairTables* pt, const EllPairTables* gt, int rp) {
-  const PrevSlot prv = prev_slot(st, rp);  // reuse_forces: sub-step 0 reads slot rp
-  const int T = blockDim.x, tid = threadIdx.x, N = st.n;
-  const size_t M = (size_t)st.m, base = (size_t)e * N;
-  const int ncell = 1 << (lx + ly);
-  const int ncx = 1 << lx, ncy = 1 << ly;
-  const int loy = ncy >= 3 ? -1 : 0, hiy = ncy >= 3 ? 1 : ncy - 1;
-  const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
-  const float sx0 = d->sx[0], sx1 = d->sx[1];
-  const float eps24 = d->eps24;
-  uint2* sq = reinterpret_cast<uint2*>(lsq + ((reinterpret_cast<uintptr_t>(lsq) >> 2) & 1));
-  float2* sdir = reinterpret_cast<float2*>(sq + N);
-  int32_t* sid = reinterpret_cast<int32_t*>(sdir + N);
-  uint32_t* lqx = reinterpret_cast<uint32_t*>(sid + N);
-  uint32_t* lqy = lqx + N;
-  int32_t* lix = reinterpret_cast<int32_t*>(lqy + N);
-  int32_t* liy = lix + N;
-  uint32_t* lan = reinterpret_cast<uint32_t*>(liy + N);
-  for (int i = tid; i < N; i += T) {
-    const size_t gi = base + i;
-    lqx[i] = st.q[gi];
-    lqy[i] = st.q[M + gi];
-    lix[i] = st.img[gi];
-    liy[i] = st.img[M + gi];
-    lan[i] = st.ang[gi];
-  }
-  __syncthreads();
-  for (int s = 0; s < n_steps; ++s) {
-    for (int c = tid; c <= ncell; c += T) cnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < N; i += T) atomicAdd(&cnt[cell_index(lqx[i], lqy[i], lx, ly)], 1);
-    __syncthreads();
-    block_exclusive_scan(cnt, ncell, wave_sums);
-    __syncthreads();
-    for (int i = tid; i < N; i += T) {
-      const uint32_t qx = lqx[i], qy = lqy[i];
-      const int pos = atomicAdd(&cnt[cell_index(qx, qy, lx, ly)], 1);
-      float sn, cs;
-      sincos_turn(lan[i], &sn, &cs);  // the sub-step's directors, once per particle
-      sq[pos] = make_uint2(qx, qy);
-      sdir[pos] = make_float2(cs, sn);
-      sid[pos] = i | ((int)st.species[i] << 24);
-    }
-    __syncthreads();  // cell c now spans [c ? cnt[c-1] : 0, cnt[c])
-    const bool last = s == n_steps - 1;
-    int any = 0;
-    for (int ps = tid; ps < N; ps += T) {
-      const int pki = sid[ps];
-      const int i = pki & 0xffffff, sik = pki >> 24;
-      const size_t gi = base + i;
-      PState pp = {lqx[i], lqy[i], lan[i], lix[i], liy[i]};
-      const float2 ui = sdir[ps];
-      int64_t ax = 0, ay = 0, at = 0;
-      int deep = 0;
-      const int c0 = cell_index(pp.qx, pp.qy, lx, ly);
-      const int cx = c0 & (ncx - 1), cy = c0 >> lx;
-      const int xa = ncx >= 3 ? max(cx - 1, 0) : 0;
-      const int xb = ncx >= 3 ? min(cx + 1, ncx - 1) : ncx - 1;
-      const int xw = ncx >= 3 ? (cx == 0 ? ncx - 1 : (cx == ncx - 1 ? 0 : -1)) : -1;
-      for (int oy = loy; oy <= hiy; ++oy) {
-        const int row = ((cy + oy + ncy) & (ncy - 1)) << lx;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          if (part == 1 && xw < 0) continue;
-          const int c_lo = row | (part == 0 ? xa : xw), c_hi = row | (part == 0 ? xb : xw);
-          const int jb = c_lo ? cnt[c_lo - 1] : 0, je = cnt[c_hi];
-          for (int jj = jb; jj < je; ++jj) {
-            if (jj == ps) continue;
-            const uint2 qj = sq[jj];
-            const float rx = (float)(int32_t)(qj.x - pp.qx) * sx0;
-            const float ry = (float)(int32_t)(qj.y - pp.qy) * sx1;
-            const int pk = sik * kMaxSpecies + (sid[jj] >> 24);
-            if (kGB) {
-              const float r2 = __builtin_fmaf(rx, rx, ry * ry);
-              if (!(r2 < gt->rcut2[pk] && r2 > 0.0f)) continue;
-              const float2 uj = sdir[jj];
-              deep += gb_pair(ea, gt->sig0[pk], gt->isig0[pk], gt->rcut[pk], r2, rx, ry, ui.x,
-                              ui.y, uj.x, uj.y, ax, ay, at)
-                          ? 1
-                          : 0;
-            } else {
-              pair_force(pt->cut2[pk], pt->sig6[pk], eps24, rx, ry, ax, ay);
-            }
-          }
-        }
-      }
-      // (counted in the sub-steps only: an overlapping start is what the
-      // overlap removal is for)
-      if (kGB && deep && !sd_mode) atomicAdd(st.wall_viol, (unsigned long long)deep);
-      const bool first = st.reuse && s == 0 && !sd_mode;  // reuse_forces: previous run's
-      const float fs = first ? prv.f[gi] : st.f_swim[gi];
-      const float tz = first ? prv.tz[gi] : st.torque_z[gi];
-      const float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
-      const PConst pc = load_pconst(d, sik);
-      if (sd_mode) {
-        const float tq = __builtin_fmaf(i64_to_f32(at), 5.9604644775390625e-08f, tz);
-        any |= sd_step(pc, pp, ax, ay, fs, tq, fex, fey, g, md) ? 1 : 0;
-      } else {
-        float vx, vy, w;
-        ell_step(ea, sik, pc, pp, ax, ay, at, fs, tz, fex, fey, k0, k1, (uint32_t)i,
-                 step0 + (uint64_t)s, last, &vx, &vy, &w, first ? prv.ang[gi] : pp.an, !first,
-                 ui.y, ui.x);
-        if (last) {
-          st.vel[gi] = vx;
-          st.vel[M + gi] = vy;
-          st.vel[2 * M + gi] = 0.0f;
-          st.omega[gi] = w;
-        }
-      }
-      lqx[i] = pp.qx;  // the sort of the next sub-step reads them after a barrier
-      lqy[i] = pp.qy;
-      lix[i] = pp.ix;
-      liy[i] = pp.iy;
-      lan[i] = pp.an;
-    }
-    if (sd_mode) {
-      if (!__syncthreads_or(any)) break;
+struct EllEnvPath : EnvPathBase {
+  static constexpr bool kDirs = true;
+  const EllArgs* __restrict__ ea;
+  const EllPairTables* gt;
+  __device__ __forceinline__ void pair(const EnvRun& r, int pk, float rx, float ry, float2 ui,
+                                       const float2* uj, EnvAcc& a) const {
+    if (kGB) {
+      const float r2 = __builtin_fmaf(rx, rx, ry * ry);
+      if (!(r2 < gt->rcut2[pk] && r2 > 0.0f)) return;
+      a.deep += gb_pair(ea, gt->sig0[pk], gt->isig0[pk], gt->rcut[pk], r2, rx, ry, ui.x, ui.y,
+                        uj->x, uj->y, a.ax, a.ay, a.at)
+                    ? 1
+                    : 0;
     } else {
-      __syncthreads();
+      EnvPathBase::pair(r, pk, rx, ry, ui, uj, a);
     }
   }
-  __syncthreads();
-  for (int i = tid; i < N; i += T) {
-    const size_t gi = base + i;
-    st.q[gi] = lqx[i];
-    st.q[M + gi] = lqy[i];
-    st.img[gi] = lix[i];
-    st.img[M + gi] = liy[i];
-    st.ang[gi] = lan[i];
+  template <class L>
+  __device__ __forceinline__ bool step(const EnvRun& r, const L&, int s, bool last,
+                                       const EnvParticle& q, PState& p, float2 ui, EnvAcc& a,
+                                       int& any) const {
+    // (counted in the sub-steps only: an overlapping start is what the
+    // overlap removal is for)
+    if (kGB && a.deep && !r.sd_mode) atomicAdd(r.st.wall_viol, (unsigned long long)a.deep);
+    const PConst pc = load_pconst(r.d, q.sik);
+    if (r.sd_mode) {
+      const float tq = __builtin_fmaf(i64_to_f32(a.at), 5.9604644775390625e-08f, q.tz);
+      any |= sd_step(pc, p, a.ax, a.ay, q.fs, tq, q.fex, q.fey, r.g, r.md) ? 1 : 0;
+    } else {
+      float vx, vy, w;
+      ell_step(ea, q.sik, pc, p, a.ax, a.ay, a.at, q.fs, q.tz, q.fex, q.fey, r.k0, r.k1,
+               (uint32_t)q.i, r.step0 + (uint64_t)s, last, &vx, &vy, &w,
+               q.first ? r.prv.ang[q.gi] : p.an, !q.first, ui.y, ui.x);
+      if (last) env_store_vel(r, q.gi, vx, vy, w);
+    }
+    return true;
   }
-}
+};
 
 // Ellipsoid-engine launch: n_steps sub-steps (or SD steps) of every env, one
 // 1024-thread workgroup per env (k_global's contract: reuse_forces slots,
@@ -333,8 +232,8 @@ __global__ __launch_bounds__(1024) void k_ellipsoid_run(
   int32_t* cnt = wave_sums + 16;
   const uint64_t step0 = sd_mode ? 0ull : *step_ctr;
   const int par = window_parity(step_ctr);
-  block_ellipsoid_run<kGB>(d, st, ea, blockIdx.x, n_steps, step0, lx, ly, sd_mode != 0, g, md,
-                           cnt, wave_sums, cnt + (1 << (lx + ly)) + 1, &pt, &gt, par);
+  block_env_run(d, st, blockIdx.x, n_steps, step0, lx, ly, sd_mode != 0, g, md, cnt, wave_sums,
+                cnt + (1 << (lx + ly)) + 1, &pt, par, EllEnvPath<kGB>{{}, ea, &gt});
   save_forces_env(st, blockIdx.x, sd_mode ? par : par ^ 1);
   if (!sd_mode) advance_counter(step_ctr, arrive, step0, n_steps);
 }

@@ -1562,6 +1562,16 @@ int swarm_engine_wall_violations(swarm_engine_t* e, uint64_t* count) {
   return SWARM_OK;
 }
 
+// An engine that takes a rod or ellipsoids: swarm::plan_no_cluster_windows,
+// and nothing pending of what a window would have used.
+static void no_cluster_windows(swarm_engine_t* e) {
+  swarm::plan_no_cluster_windows(e->plan);
+  e->defer_hint = false;
+  e->prebuilt = false;
+  e->prebuilt_noise_steps = 0;
+  e->ride_stage = 0;
+}
+
 int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   if (!e || !rod) return fail(SWARM_EINVAL, "null argument");
   if (const int frc = flush_check(e)) return frc;
@@ -1585,7 +1595,8 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   const double half = 0.5 * (rod->n - 1) * rod->delta;
   if (!(half < 0.49 * std::min(e->params.box[0], e->params.box[1])))
     return fail(SWARM_EINVAL, "the rod must be shorter than the box");
-  const size_t lds = swarm::rod_lds_words(e->n, 1 << (e->plan.lxg + e->plan.lyg)) * 4;
+  const size_t lds =
+      swarm::env_lds_words(e->n, 1 << (e->plan.lxg + e->plan.lyg), false, swarm::kRodTailWords) * 4;
   if (lds + sizeof(swarm::PairTables) > kMaxLds)
     return fail(SWARM_ECAPACITY, "env does not fit the LDS of one workgroup");
   e->rod.first = rod->first;
@@ -1593,18 +1604,7 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   e->rod.delta = (float)rod->delta;
   e->rod.fixed = rod->fixed ? 1 : 0;
   e->has_rod = true;
-  // no cluster windows, and none of what prepares or checks them: the one
-  // place that rewrites the plan after creation
-  e->plan.cluster_path = false;
-  e->plan.nlist_path = false;
-  e->plan.noise_table = false;
-  e->plan.wide_run = false;
-  e->plan.env_build = false;
-  e->plan.defer_check = false;
-  e->defer_hint = false;
-  e->prebuilt = false;
-  e->prebuilt_noise_steps = 0;
-  e->ride_stage = 0;
+  no_cluster_windows(e);
   if (const int rc = launch_rod_snap(e)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
   return SWARM_OK;
@@ -1643,7 +1643,7 @@ int swarm_engine_set_ellipsoids(swarm_engine_t* e, const swarm_ellipsoids_t* ell
   }
   const size_t fixed = swarm::kEllStaticLds;
   auto fits = [&](int n, int gx, int gy) {
-    return swarm::ell_lds_words(n, 1 << (gx + gy)) * 4 + fixed <= kMaxLds;
+    return swarm::env_lds_words(n, 1 << (gx + gy), true, 0) * 4 + fixed <= kMaxLds;
   };
   if (!fits(e->n, lx, ly)) {
     // 40 bytes of state per particle beside the cell counts and the pair
@@ -1688,20 +1688,9 @@ int swarm_engine_set_ellipsoids(swarm_engine_t* e, const swarm_ellipsoids_t* ell
   HIP_TRY(hipStreamSynchronize(e->stream));  // (a is a local)
   e->has_ell = true;
   e->ell_gb = gb;
-  // as swarm_engine_set_rod: no cluster windows, and none of what prepares
-  // or checks them
   e->plan.lxg = lx;
   e->plan.lyg = ly;
-  e->plan.cluster_path = false;
-  e->plan.nlist_path = false;
-  e->plan.noise_table = false;
-  e->plan.wide_run = false;
-  e->plan.env_build = false;
-  e->plan.defer_check = false;
-  e->defer_hint = false;
-  e->prebuilt = false;
-  e->prebuilt_noise_steps = 0;
-  e->ride_stage = 0;
+  no_cluster_windows(e);
   return SWARM_OK;
 }
 

@@ -127,7 +127,8 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
   }
   if (e->has_rod) {
     hipLaunchKernelGGL(swarm::k_rod_run, dim3(e->n_envs), dim3(1024),
-                       swarm::rod_lds_words(e->n, 1 << (pl.lxg + pl.lyg)) * 4, e->stream,
+                       swarm::env_lds_words(e->n, 1 << (pl.lxg + pl.lyg), false,
+                                            swarm::kRodTailWords) * 4, e->stream,
                        e->d_derived, e->st, e->rod, n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg,
                        sd_mode, g, md);
     HIP_TRY(hipGetLastError());
@@ -136,7 +137,7 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
   if (e->has_ell) {
     bools([&](auto gb) {
       hipLaunchKernelGGL(swarm::k_ellipsoid_run<gb>, dim3(e->n_envs), dim3(1024),
-                         swarm::ell_lds_words(e->n, 1 << (pl.lxg + pl.lyg)) * 4, e->stream,
+                         swarm::env_lds_words(e->n, 1 << (pl.lxg + pl.lyg), true, 0) * 4, e->stream,
                          e->d_derived, e->st, e->d_ell, n_steps, e->d_step, e->d_arrive, pl.lxg,
                          pl.lyg, sd_mode, g, md);
     }, e->ell_gb);

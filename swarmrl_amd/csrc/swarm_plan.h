@@ -173,6 +173,18 @@ struct EnginePlan {
   size_t count[kNumEngineBufs] = {};
 };
 
+// An engine whose every sub-step runs on one workgroup per env (a rod,
+// ellipsoids): no cluster windows, and none of what prepares or checks them.
+// The one rewrite of a plan after creation.
+inline void plan_no_cluster_windows(EnginePlan& pl) {
+  pl.cluster_path = false;
+  pl.nlist_path = false;
+  pl.noise_table = false;
+  pl.wide_run = false;
+  pl.env_build = false;
+  pl.defer_check = false;
+}
+
 inline int ilog2_floor(double v) {
   int l = 0;
   while ((double)(1 << (l + 1)) <= v && l < 20) ++l;

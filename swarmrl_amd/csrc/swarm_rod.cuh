@@ -10,9 +10,9 @@
 //   m_k = (-1)^k (k / 2 + 1)      at      centre + m_k delta u,
 // u the centre's director.  A rigid body needs, per sub-step, the sum of all
 // of its contacts -- a reduction the cluster windows cannot provide -- so an
-// engine with a rod runs every sub-step on k_rod_run, one workgroup per env,
-// modelled on the LDS-resident global path (block_global_run_lds): the same
-// per-sub-step cell sort, pair_force / bd_step / sd_step and int64 sums.
+// engine with a rod runs every sub-step on k_rod_run, one workgroup per env:
+// a path of block_env_run (swarm_env_block.cuh), the LDS-resident global
+// path's per-sub-step cell sort, pair_force / bd_step / sd_step and int64 sums.
 // Per sub-step the rod adds
 //   F = sum_b A_b,  S = sum_b m_b A_b          (int64, 2^-24 units, LDS atomics:
 //                                               independent of contact order)
@@ -43,12 +43,11 @@ __host__ __device__ inline int rod_slot(int b) {
   return (k & 1 ? -1 : 1) * (k / 2 + 1);
 }
 
-// Dynamic LDS of k_rod_run in 4-byte words: wave sums, cell counts, the
-// sorted copy and particle state of block_global_run_lds (8 N + 2), then
-// (8-byte aligned) the rod's four int64 sums and the centre's velocities.
-__host__ __device__ inline size_t rod_lds_words(int n, int ncell) {
-  return 16 + (size_t)ncell + 1 + 8 * (size_t)n + 2 + 2 + 8 + 4;
-}
+// What k_rod_run keeps after the particle state (EnvLds::tail, the last
+// argument of env_lds_words), in 4-byte words: the plain layout's spare word,
+// two for the alignment to 8 bytes, the rod's four int64 sums and the centre's
+// velocities (v_x, v_y, omega and a pad).
+constexpr size_t kRodTailWords = 1 + 2 + 8 + 4;
 
 // Bead b (1 <= b < rn) from the centre's state: per axis
 //   dq = f2i32_sat(((m delta) cos|sin) inv_sx)
@@ -68,135 +67,57 @@ __device__ __forceinline__ void rod_place(const RodArgs& rod, int b, uint32_t cq
   advance(p.qy, p.iy, f2i32_sat(*ry * inv_sx1));
 }
 
-// All sub-steps (or steepest-descent steps) of env e by one workgroup.
-__device__ __forceinline__ void block_rod_run(const Derived* __restrict__ d, const DevState& st,
-                                              const RodArgs rod, int e, int n_steps,
-                                              uint64_t step0, int lx, int ly, bool sd_mode,
-                                              float g, float md, int32_t* cnt, int32_t* wave_sums,
-                                              int32_t* lsq, const PairTables* pt, int rp) {
-  const PrevSlot prv = prev_slot(st, rp);  // reuse_forces: sub-step 0 reads slot rp
-  const int T = blockDim.x, tid = threadIdx.x, N = st.n;
-  const size_t M = (size_t)st.m, base = (size_t)e * N;
-  const int ncell = 1 << (lx + ly);
-  const int ncx = 1 << lx, ncy = 1 << ly;
-  const int loy = ncy >= 3 ? -1 : 0, hiy = ncy >= 3 ? 1 : ncy - 1;
-  const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
-  const float sx0 = d->sx[0], sx1 = d->sx[1];
-  const float inv_sx0 = d->inv_sx[0], inv_sx1 = d->inv_sx[1];
-  const float eps24 = d->eps24;
-  const int r0 = rod.first, r1 = rod.first + rod.n;
-  uint2* sq = reinterpret_cast<uint2*>(lsq + ((reinterpret_cast<uintptr_t>(lsq) >> 2) & 1));
-  int32_t* sid = reinterpret_cast<int32_t*>(sq + N);
-  uint32_t* lqx = reinterpret_cast<uint32_t*>(sid + N);
-  uint32_t* lqy = lqx + N;
-  int32_t* lix = reinterpret_cast<int32_t*>(lqy + N);
-  int32_t* liy = lix + N;
-  uint32_t* lan = reinterpret_cast<uint32_t*>(liy + N);
-  // the rod's sums (F_x, F_y, S_x, S_y) and the centre's (v_x, v_y, omega)
-  int32_t* tail = reinterpret_cast<int32_t*>(lan + N);
-  unsigned long long* acc =
-      reinterpret_cast<unsigned long long*>(tail + ((reinterpret_cast<uintptr_t>(tail) >> 2) & 1));
-  float* cv = reinterpret_cast<float*>(acc + 4);
-  for (int i = tid; i < N; i += T) {
-    const size_t gi = base + i;
-    lqx[i] = st.q[gi];
-    lqy[i] = st.q[M + gi];
-    lix[i] = st.img[gi];
-    liy[i] = st.img[M + gi];
-    lan[i] = st.ang[gi];
+// block_env_run with a rod: rod-rod pairs are skipped, a rod particle only
+// adds its pair sum to the rod's, and after the colloids' step the centre
+// takes its own and the beads follow it.
+struct RodEnvPath : EnvPathBase {
+  RodArgs rod;
+  float inv_sx0, inv_sx1;
+  // the rod's sums (F_x, F_y, S_x, S_y); after them the centre's (v_x, v_y, omega)
+  template <class L>
+  __device__ __forceinline__ unsigned long long* sums(const L& l) const {
+    return reinterpret_cast<unsigned long long*>(
+        l.tail + ((reinterpret_cast<uintptr_t>(l.tail) >> 2) & 1));
   }
-  __syncthreads();
-  for (int s = 0; s < n_steps; ++s) {
-    for (int c = tid; c <= ncell; c += T) cnt[c] = 0;
-    if (tid < 4) acc[tid] = 0ull;
-    __syncthreads();
-    for (int i = tid; i < N; i += T) atomicAdd(&cnt[cell_index(lqx[i], lqy[i], lx, ly)], 1);
-    __syncthreads();
-    block_exclusive_scan(cnt, ncell, wave_sums);
-    __syncthreads();
-    for (int i = tid; i < N; i += T) {
-      const uint32_t qx = lqx[i], qy = lqy[i];
-      const int pos = atomicAdd(&cnt[cell_index(qx, qy, lx, ly)], 1);
-      sq[pos] = make_uint2(qx, qy);
-      sid[pos] = i | ((int)st.species[i] << 24);
+  __device__ __forceinline__ bool in_rod(int i) const {
+    return i >= rod.first && i < rod.first + rod.n;
+  }
+  template <class L>
+  __device__ __forceinline__ void begin_step(const L& l) const {
+    if (threadIdx.x < 4) sums(l)[threadIdx.x] = 0ull;
+  }
+  // rod-rod: internal to the rigid body
+  __device__ __forceinline__ bool skip(int i, int j) const { return in_rod(i) && in_rod(j); }
+  template <class L>
+  __device__ __forceinline__ bool step(const EnvRun& r, const L& l, int s, bool last,
+                                       const EnvParticle& q, PState& p, float2, EnvAcc& a,
+                                       int& any) const {
+    if (!in_rod(q.i)) {
+      env_colloid_step(r, s, last, q, p, a.ax, a.ay, any);
+      return true;
     }
-    __syncthreads();  // cell c now spans [c ? cnt[c-1] : 0, cnt[c])
-    const bool last = s == n_steps - 1;
-    int any = 0;
-    for (int ps = tid; ps < N; ps += T) {
-      const int pki = sid[ps];
-      const int i = pki & 0xffffff, sik = pki >> 24;
-      const bool in_rod = i >= r0 && i < r1;
-      const size_t gi = base + i;
-      PState pp = {lqx[i], lqy[i], lan[i], lix[i], liy[i]};
-      int64_t ax = 0, ay = 0;
-      const int c0 = cell_index(pp.qx, pp.qy, lx, ly);
-      const int cx = c0 & (ncx - 1), cy = c0 >> lx;
-      const int xa = ncx >= 3 ? max(cx - 1, 0) : 0;
-      const int xb = ncx >= 3 ? min(cx + 1, ncx - 1) : ncx - 1;
-      const int xw = ncx >= 3 ? (cx == 0 ? ncx - 1 : (cx == ncx - 1 ? 0 : -1)) : -1;
-      for (int oy = loy; oy <= hiy; ++oy) {
-        const int row = ((cy + oy + ncy) & (ncy - 1)) << lx;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          if (part == 1 && xw < 0) continue;
-          const int c_lo = row | (part == 0 ? xa : xw), c_hi = row | (part == 0 ? xb : xw);
-          const int jb = c_lo ? cnt[c_lo - 1] : 0, je = cnt[c_hi];
-          for (int jj = jb; jj < je; ++jj) {
-            const int pj = sid[jj];
-            const int j = pj & 0xffffff;
-            if (j == i) continue;
-            if (in_rod && j >= r0 && j < r1) continue;  // rod-rod: internal to the rigid body
-            const uint2 qj = sq[jj];
-            const float rx = (float)(int32_t)(qj.x - pp.qx) * sx0;
-            const float ry = (float)(int32_t)(qj.y - pp.qy) * sx1;
-            const int pk = sik * kMaxSpecies + (pj >> 24);
-            pair_force(pt->cut2[pk], pt->sig6[pk], eps24, rx, ry, ax, ay);
-          }
-        }
-      }
-      if (in_rod) {
-        // the rod moves as one body: its particles only add to the sums
-        if (!sd_mode && (ax != 0 || ay != 0)) {
-          const int64_t m = (int64_t)rod_slot(i - r0);
-          atomicAdd(&acc[0], (unsigned long long)ax);
-          atomicAdd(&acc[1], (unsigned long long)ay);
-          atomicAdd(&acc[2], (unsigned long long)(m * ax));
-          atomicAdd(&acc[3], (unsigned long long)(m * ay));
-        }
-        continue;
-      }
-      const bool first = st.reuse && s == 0 && !sd_mode;  // reuse_forces: previous run's
-      const float fs = first ? prv.f[gi] : st.f_swim[gi];
-      const float tz = first ? prv.tz[gi] : st.torque_z[gi];
-      const float fex = st.f_ext[gi], fey = st.f_ext[M + gi];
-      const PConst pc = load_pconst(d, sik);
-      if (sd_mode) {
-        any |= sd_step(pc, pp, ax, ay, fs, tz, fex, fey, g, md) ? 1 : 0;
-      } else {
-        float vx, vy, w;
-        bd_step(pc, pp, ax, ay, fs, tz, fex, fey, k0, k1, (uint32_t)i, step0 + (uint64_t)s, last,
-                &vx, &vy, &w, first ? prv.ang[gi] : pp.an);
-        if (last) {
-          st.vel[gi] = vx;
-          st.vel[M + gi] = vy;
-          st.vel[2 * M + gi] = 0.0f;
-          st.omega[gi] = w;
-        }
-      }
-      lqx[i] = pp.qx;  // the sort of the next sub-step reads lqx/lqy after a barrier
-      lqy[i] = pp.qy;
-      lix[i] = pp.ix;
-      liy[i] = pp.iy;
-      lan[i] = pp.an;
+    // the rod moves as one body (and not at all in the overlap removal): its
+    // particles only add to the sums
+    if (!r.sd_mode && (a.ax != 0 || a.ay != 0)) {
+      unsigned long long* acc = sums(l);
+      const int64_t m = (int64_t)rod_slot(q.i - rod.first);
+      atomicAdd(&acc[0], (unsigned long long)a.ax);
+      atomicAdd(&acc[1], (unsigned long long)a.ay);
+      atomicAdd(&acc[2], (unsigned long long)(m * a.ax));
+      atomicAdd(&acc[3], (unsigned long long)(m * a.ay));
     }
-    if (sd_mode) {  // the rod does not move in the overlap removal
-      if (!__syncthreads_or(any)) break;
-      continue;
-    }
-    __syncthreads();  // the rod's sums are complete
-    if (tid == 0) {   // the centre: one bd_step from (F, tau), its own noise stream
-      PState pc_ = {lqx[r0], lqy[r0], lan[r0], lix[r0], liy[r0]};
+    return false;
+  }
+  // (the sub-step's barrier: the rod's sums are complete)
+  template <class L>
+  __device__ __forceinline__ void end_step(const EnvRun& r, const L& l, int s, bool last) const {
+    const int T = blockDim.x, tid = threadIdx.x, r0 = rod.first;
+    const size_t base = r.base;
+    const DevState& st = r.st;
+    unsigned long long* acc = sums(l);
+    float* cv = reinterpret_cast<float*>(acc + 4);
+    if (tid == 0) {  // the centre: one bd_step from (F, tau), its own noise stream
+      PState pc_ = {l.qx[r0], l.qy[r0], l.an[r0], l.ix[r0], l.iy[r0]};
       const PState old = pc_;
       float sn, cs;
       sincos_turn(pc_.an, &sn, &cs);
@@ -204,10 +125,10 @@ __device__ __forceinline__ void block_rod_run(const Derived* __restrict__ d, con
       const float t1 = cs * Sy, t2 = sn * Sx;
       const float cr = t1 - t2;
       const float tau = (rod.delta * cr) * 5.9604644775390625e-08f;
-      const PConst pc = load_pconst(d, (int)st.species[r0]);
+      const PConst pc = load_pconst(r.d, (int)st.species[r0]);
       float vx = 0.0f, vy = 0.0f, w = 0.0f;
-      bd_step(pc, pc_, (int64_t)acc[0], (int64_t)acc[1], 0.0f, tau, 0.0f, 0.0f, k0, k1,
-              (uint32_t)r0, step0 + (uint64_t)s, last, &vx, &vy, &w, pc_.an);
+      bd_step(pc, pc_, (int64_t)acc[0], (int64_t)acc[1], 0.0f, tau, 0.0f, 0.0f, r.k0, r.k1,
+              (uint32_t)r0, r.step0 + (uint64_t)s, last, &vx, &vy, &w, pc_.an);
       if (rod.fixed) {  // no translation and no translational velocity
         pc_.qx = old.qx;
         pc_.qy = old.qy;
@@ -216,56 +137,40 @@ __device__ __forceinline__ void block_rod_run(const Derived* __restrict__ d, con
         vx = 0.0f;
         vy = 0.0f;
       }
-      lqx[r0] = pc_.qx;
-      lqy[r0] = pc_.qy;
-      lix[r0] = pc_.ix;
-      liy[r0] = pc_.iy;
-      lan[r0] = pc_.an;
+      l.qx[r0] = pc_.qx;
+      l.qy[r0] = pc_.qy;
+      l.ix[r0] = pc_.ix;
+      l.iy[r0] = pc_.iy;
+      l.an[r0] = pc_.an;
       if (last) {
         cv[0] = vx;
         cv[1] = vy;
         cv[2] = w;
-        st.vel[base + r0] = vx;
-        st.vel[M + base + r0] = vy;
-        st.vel[2 * M + base + r0] = 0.0f;
-        st.omega[base + r0] = w;
+        env_store_vel(r, base + r0, vx, vy, w);
       }
     }
     __syncthreads();  // the centre's new state
     for (int b = 1 + tid; b < rod.n; b += T) {
       float sn, cs, rx, ry;
-      sincos_turn(lan[r0], &sn, &cs);
+      sincos_turn(l.an[r0], &sn, &cs);
       PState pb;
-      rod_place(rod, b, lqx[r0], lqy[r0], lix[r0], liy[r0], sn, cs, inv_sx0, inv_sx1, pb, &rx,
+      rod_place(rod, b, l.qx[r0], l.qy[r0], l.ix[r0], l.iy[r0], sn, cs, inv_sx0, inv_sx1, pb, &rx,
                 &ry);
       const int i = r0 + b;
-      lqx[i] = pb.qx;
-      lqy[i] = pb.qy;
-      lix[i] = pb.ix;
-      liy[i] = pb.iy;
-      lan[i] = lan[r0];
+      l.qx[i] = pb.qx;
+      l.qy[i] = pb.qy;
+      l.ix[i] = pb.ix;
+      l.iy[i] = pb.iy;
+      l.an[i] = l.an[r0];
       if (last) {  // v_b = v_c + omega x r_b
         const float w = cv[2];
-        const size_t gi = base + i;
-        st.vel[gi] = cv[0] - w * ry;
-        st.vel[M + gi] = cv[1] + w * rx;
-        st.vel[2 * M + gi] = 0.0f;
-        st.omega[gi] = w;
+        env_store_vel(r, base + i, cv[0] - w * ry, cv[1] + w * rx, w);
       }
     }
     // (no barrier here: the next sub-step zeroes cnt and the sums, which
     // nobody reads any more, and meets a barrier before it reads positions)
   }
-  __syncthreads();
-  for (int i = tid; i < N; i += T) {
-    const size_t gi = base + i;
-    st.q[gi] = lqx[i];
-    st.q[M + gi] = lqy[i];
-    st.img[gi] = lix[i];
-    st.img[M + gi] = liy[i];
-    st.ang[gi] = lan[i];
-  }
-}
+};
 
 // Rod-engine launch: n_steps sub-steps (or SD steps) of every env, one
 // 1024-thread workgroup per env (k_global's contract: reuse_forces slots,
@@ -282,8 +187,9 @@ __global__ __launch_bounds__(1024) void k_rod_run(const Derived* __restrict__ d,
   int32_t* cnt = wave_sums + 16;
   const uint64_t step0 = sd_mode ? 0ull : *step_ctr;
   const int par = window_parity(step_ctr);
-  block_rod_run(d, st, rod, blockIdx.x, n_steps, step0, lx, ly, sd_mode != 0, g, md, cnt,
-                wave_sums, cnt + (1 << (lx + ly)) + 1, &pt, par);
+  block_env_run(d, st, blockIdx.x, n_steps, step0, lx, ly, sd_mode != 0, g, md, cnt, wave_sums,
+                cnt + (1 << (lx + ly)) + 1, &pt, par,
+                RodEnvPath{{}, rod, d->inv_sx[0], d->inv_sx[1]});
   save_forces_env(st, blockIdx.x, sd_mode ? par : par ^ 1);
   if (!sd_mode) advance_counter(step_ctr, arrive, step0, n_steps);
 }

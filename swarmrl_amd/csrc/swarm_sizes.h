@@ -51,11 +51,21 @@ SWARM_HD inline int slots_per_env(int n, bool one_pass = false) {
   return (one_pass ? 4 : 2) * n + 64 * 66;
 }
 
-// LDS words the register-resident global path needs after the cell counts
-// (sorted positions as uint2 + ids), 0 when it does not apply (3-D, or more
-// than kGlobalCH particles per thread of a 1024-thread block).
+// Dynamic LDS of a workgroup that runs block_env_run (swarm_env_block.cuh),
+// in 4-byte words: wave sums, cell counts, a word to align what follows to 8
+// bytes, the sorted positions (uint2), with dirs the sorted directors
+// (float2), the sorted ids, the particle state (q, img, ang: 5 words), then
+// the tail_words a path keeps of its own.
+SWARM_HD inline size_t env_lds_words(int n, int ncell, bool dirs, size_t tail_words) {
+  return 16 + (size_t)ncell + 1 + 1 + (dirs ? 10 : 8) * (size_t)n + tail_words;
+}
+
+// LDS words the LDS-resident global path needs after the cell counts (with
+// one spare word, which the capacity thresholds below have always counted),
+// 0 when it does not apply (3-D, or more than kGlobalCH particles per thread
+// of a 1024-thread block).
 SWARM_HD inline size_t global_lds_extra_words(int n, int dims, int ncell) {
-  const size_t extra = 8 * (size_t)n + 2;
+  const size_t extra = env_lds_words(n, ncell, false, 1) - (16 + (size_t)ncell + 1);
   // k_check's layout (the larger): 16 + 16 + 1024 + ncell + 1 words first,
   // and 4 KB of static LDS beside it
   const bool fits = (16 + 16 + 1024 + (size_t)ncell + 1 + extra) * 4 + 4096 <= kMaxLds;

@@ -258,9 +258,12 @@ static AllocSum alloc_sum(const EnginePlan& pl) {
   return a;
 }
 
-static void print_plan(const Row& r, const EnginePlan& pl) {
+// every EnginePlan field and the allocations' summary (a static buffer)
+static const char* plan_line(const Row& r, const EnginePlan& pl) {
+  static char line[1024];
   const AllocSum a = alloc_sum(pl);
-  std::printf("%s: ok g=%d,%d,%d b=%d,%d,%d lat=%d cluster=%d nlist=%d big=%d chip=%d luf=%d "
+  std::snprintf(line, sizeof(line),
+              "%s: ok g=%d,%d,%d b=%d,%d,%d lat=%d cluster=%d nlist=%d big=%d chip=%d luf=%d "
               "mwb=%d onep=%d fill=%d noise=%d envb=%d wide=%d rot=%d l1=%d defer=%d cap=%d S=%d "
               "wmax=%d stage=%d nb=%d wpb=%d cd=%.9g allocs=%d bytes=%llu sum=%016llx\n",
               r.name, pl.lxg, pl.lyg, pl.lzg, pl.lxb, pl.lyb, pl.lzb, (int)pl.latency_bound,
@@ -269,6 +272,11 @@ static void print_plan(const Row& r, const EnginePlan& pl) {
               (int)pl.noise_table, (int)pl.env_build, (int)pl.wide_run, (int)pl.rot_helper,
               (int)pl.l1_pairs, (int)pl.defer_check, pl.pair_cap, pl.S, pl.wmax, pl.sort_stage_k,
               pl.noise_blocks, pl.run_wpb, (double)(float)pl.cand_disp, a.n, a.bytes, a.sum);
+  return line;
+}
+
+static void print_plan(const Row& r, const EnginePlan& pl) {
+  std::fputs(plan_line(r, pl), stdout);
 }
 
 // What holds on every valid row, whatever the table says.
@@ -337,6 +345,39 @@ static void check_thresholds() {
         swarm::build_lds_words_big(kLastClusterBuild + 1) * 4 > kMaxLds);
   CHECK(!staged(kFirstStagedSort - 1) && staged(kFirstStagedSort));
   CHECK(staged(kLastStagedSort) && !staged(kLastStagedSort + 1));
+  // env_lds_words against the three formulas it replaced, written out: the
+  // global path's extra words (kRodTailWords of swarm_rod.cuh is 15), the
+  // rod's and the ellipsoids' whole dynamic LDS
+  for (const int n : {1, 2, 63, 64, 1024, 1131, 4096})
+    for (const int ncell : {1, 4, 64, 4096}) {
+      const size_t N = (size_t)n, C = (size_t)ncell;
+      CHECK(swarm::env_lds_words(n, ncell, false, 1) - (16 + C + 1) == 8 * N + 2);
+      CHECK(swarm::global_lds_extra_words(n, 2, ncell) == 8 * N + 2);
+      CHECK(swarm::global_lds_extra_words(n, 3, ncell) == 0);
+      CHECK(swarm::env_lds_words(n, ncell, false, 15) == 16 + C + 1 + 8 * N + 2 + 2 + 8 + 4);
+      CHECK(swarm::env_lds_words(n, ncell, true, 0) == 16 + C + 1 + 1 + 10 * N);
+    }
+  // plan_no_cluster_windows clears these six flags and touches nothing else
+  {
+    EnginePlan pl;
+    const char* msg = "";
+    const swarm_params_t p = params_of(bench("", 1, 4096));
+    CHECK(swarm::plan_engine(p, 1, 4096, {}, swarm::kPairTablesBytes, &pl, &msg) == SWARM_OK);
+    CHECK(pl.cluster_path && pl.noise_table && pl.wide_run && pl.defer_check);
+    pl.nlist_path = pl.env_build = true;  // (no one plan sets all six)
+    EnginePlan want = pl;
+    want.cluster_path = want.nlist_path = want.noise_table = false;
+    want.wide_run = want.env_build = want.defer_check = false;
+    swarm::plan_no_cluster_windows(pl);
+    const Row r = bench("no_cluster_windows", 1, 4096);
+    char got_line[1024], want_line[1024];
+    std::snprintf(got_line, sizeof(got_line), "%s", plan_line(r, pl));
+    std::snprintf(want_line, sizeof(want_line), "%s", plan_line(r, want));
+    CHECK(std::strcmp(got_line, want_line) == 0);
+    CHECK(std::memcmp(pl.count, want.count, sizeof(pl.count)) == 0);
+    CHECK(!pl.cluster_path && !pl.nlist_path && !pl.noise_table && !pl.wide_run &&
+          !pl.env_build && !pl.defer_check);
+  }
   // the four parsing rules, over unset, '0', '1' and anything else
   for (const bool v : {false, true}) {
     CHECK(swarm::ov_clears(0, v) == v && !swarm::ov_clears('0', v) &&

@@ -39,7 +39,8 @@ def _harness(box, species_of, n_envs, kappa, reuse=False, kT=KT, seed=17, n_spec
     from gpu_harness import Harness
     from swarmrl_amd import _capi
 
-    h = Harness([box, box, box], DT, kT, EPS, seed, SPECIES[:n_species], species_of,
+    h = Harness(list(box) if np.ndim(box) else [box, box, box], DT, kT, EPS, seed,
+                SPECIES[:n_species], species_of,
                 n_envs=n_envs, reuse=reuse)
     cell = _capi.SwarmEllipsoids()
     cell.aspect_ratio = kappa
@@ -153,6 +154,26 @@ def test_pairs_across_the_periodic_boundary():
     cut = 6.0 / 32.0 * TWO32
     assert np.any(states[0]["q"][0] < cut) and np.any(states[0]["q"][0] > TWO32 - cut)
     _run_bit_exact(h, ell, states, np.zeros(96, int), False)
+
+
+def test_grid_of_two_cells():
+    """A 20 x 50 um box with the cutoff of 6: 2 x 8 cells, so both cells of a
+    stencil row are one range and there is no wrap range.  16 prolate
+    spheroids on a 4 x 4 lattice 5 um apart (also through the periodic
+    boundary in x), jittered by 0.9."""
+    rng = np.random.default_rng(107)
+    n, box = 16, [20.0, 50.0, 50.0]
+    h, ell = _harness(box, np.zeros(n, int), 2, 3.0, reuse=True)
+    assert oracle.cell_grid(h.op, n, 6.0) == (1, 3)
+    states = []
+    for _ in range(2):
+        k = np.arange(n)
+        pos = np.stack([2.5 + 5.0 * (k % 4), 17.5 + 5.0 * (k // 4), np.zeros(n)], 1)
+        pos[:, :2] += rng.uniform(-0.9, 0.9, (n, 2))
+        th = rng.uniform(0.0, 2.0 * np.pi, n)
+        states.append(oracle.state_from_positions(
+            pos, np.stack([np.cos(th), np.sin(th), np.zeros(n)], 1), box))
+    _run_bit_exact(h, ell, states, np.zeros(n, int), True)
 
 
 def test_spheres_with_per_axis_friction():

@@ -5,7 +5,7 @@ integrator kernel that reads it, bit for bit against the CPU oracle run with
 the same numbers:
 
   block_global_run      k_global, non-periodic boxes (BD and overlap removal)
-  block_global_run_lds  k_global, periodic 2-D (overlap removal; exact re-run)
+  block_env_run         k_global, periodic 2-D (overlap removal; exact re-run)
   run_wave              k_cluster_run / k_cluster_run_wide
   run_big_clusters      the check workgroup's big-cluster run
   k_nl_step2            2-D neighbour-list window
@@ -183,7 +183,7 @@ def test_big_clusters_external_force_bit_exact():
 
 @pytest.mark.parametrize("reuse", [False, True])
 def test_exact_rerun_external_force_bit_exact(reuse):
-    """block_global_run_lds as the exact re-run: in the same box one window's
+    """block_env_run as the exact re-run: in the same box one window's
     external force is +-300 force units along x on the two halves of the
     colloids (6 um in 100 sub-steps, past the skin), so the decomposition
     check fails and the window runs again from its snapshot on the global
@@ -376,11 +376,71 @@ def test_global_path_sedimentation_onto_a_wall_bit_exact(monkeypatch):
     assert not np.array_equal(plain["q"], states[0]["q"])
 
 
+@pytest.mark.parametrize("case", ["two_cells", "two_per_thread"])
+def test_lds_global_path_narrow_grid_and_two_particles_per_thread(case, monkeypatch):
+    """k_global's LDS-resident sub-steps where the stencil and the particle
+    loop take their other arms, 2 envs each, an external force set.
+    two_cells: 12 colloids of radius 1 on a 3 x 4 lattice in a periodic
+    6 x 40 um box, a grid of 2 x 16 cells: both cells of a row are one range
+    and there is no wrap range; columns 2 um apart, also through the periodic
+    boundary.  (A box this narrow has no cluster path.)
+    two_per_thread: 1100 colloids of radius 0.5, 1.05 um apart, in a 100 um
+    box with the cluster path switched off: a thread steps two of them.
+    Pairs are inside the cutoff before and after the run."""
+    from gpu_harness import Harness, species_list
+
+    rng = np.random.default_rng(108)
+    E = 2
+    if case == "two_cells":
+        n, box, radius, species = 12, [6.0, 40.0, 40.0], 1.0, species_list()[:1]
+        g = np.stack(np.meshgrid(np.arange(3), np.arange(4), indexing="ij"), -1).reshape(-1, 2)
+        lattice = np.array([1.0, 12.0]) + g * np.array([2.0, 2.05])
+    else:
+        monkeypatch.setenv("SWARMRL_AMD_CLUSTER_PATH", "0")
+        n, box, radius = 1100, [100.0, 100.0, 100.0], 0.5
+        species = [(0.5, 4.0, 6.0, 1.0e-6, 4.0e-7)]
+        g = np.stack(np.meshgrid(np.arange(34), np.arange(34), indexing="ij"), -1).reshape(-1, 2)
+        lattice = 30.0 + g[:n] * 1.05
+    sp = np.zeros(n, int)
+    states = []
+    for _ in range(E):
+        pos = np.zeros((n, 3))
+        pos[:, :2] = lattice + rng.uniform(-0.1, 0.1, (n, 2))
+        th = 2 * np.pi * rng.random(n)
+        states.append(oracle.state_from_positions(
+            pos, np.stack([np.cos(th), np.sin(th), np.zeros(n)], 1), box))
+    h = Harness(box, 1e-3, 1.0239, 1.0239, 12, species, sp, n_envs=E)
+    assert oracle.cell_grid(h.op, n, 2 * radius) == ((1, 4) if case == "two_cells" else (5, 5))
+    h.upload(states)
+    f_ext = _forces(rng, E, n, 1.0)
+    h.set_external_force(f_ext)
+    touching = [len(oracle.neighbor_pairs(h.op, s, 2 * radius)) for s in states]
+    step = 0
+    for nsteps in (12, 1):
+        f = rng.uniform(1.0, 4.0, E * n).astype(np.float32)
+        t = rng.normal(size=E * n).astype(np.float32) * 5
+        h.set_actions(f, t)
+        h.integrate(nsteps)
+        vels = []
+        for e in range(E):
+            s = slice(e * n, (e + 1) * n)
+            states[e], v, _ = oracle.bd_run(h.op, states[e], sp, f[s], t[s], nsteps, step0=step,
+                                            env=e, f_ext=_fe(f_ext, e))
+            vels.append(v)
+        step += nsteps
+        _compare(h, states, vels)
+        fb, waves = h.window_stats()
+        assert np.all(waves == 0) and np.all(fb == 0), (fb, waves)
+    touching += [len(oracle.neighbor_pairs(h.op, s, 2 * radius)) for s in states]
+    print("lds global path", case, "pairs inside the cutoff", touching)
+    assert min(touching) >= n // 4, touching
+
+
 # ------------------------------------------------------ 6. overlap removal
 def test_overlap_removal_2d_external_force_bit_exact():
     """swarm_engine_remove_overlap with the force set (SwarmEngine uploads it
     before its overlap removal): k_global's steepest descent on a periodic
-    2-D box (block_global_run_lds), 3 dense envs of two species."""
+    2-D box (block_env_run), 3 dense envs of two species."""
     from gpu_harness import Harness, random_state, species_list
 
     rng = np.random.default_rng(107)

@@ -6,7 +6,7 @@ one sub-step at a time with f_ext + F(q) (tests/potential_ref.py):
 
   run_wave              k_cluster_run / k_cluster_run_wide, table / in-kernel normals
   run_big_clusters      the check workgroup's big-cluster run
-  block_global_run_lds  the exact re-run (and the periodic 2-D overlap removal)
+  block_env_run         the exact re-run (and the periodic 2-D overlap removal)
   k_nl_step2            2-D neighbour-list window
   block_global_run      non-periodic boxes (BD and overlap removal), with walls too
   block_global_run3     k_global3 (BD and overlap removal)
@@ -375,7 +375,7 @@ def test_big_clusters_potential_bit_exact():
 
 @pytest.mark.parametrize("reuse", [False, True])
 def test_exact_rerun_potential_bit_exact(reuse):
-    """block_global_run_lds as the exact re-run: the second window's potential
+    """block_env_run as the exact re-run: the second window's potential
     carries a tent of slope -+300 force units on the two halves of the box
     (6 um in 100 sub-steps, past the skin), replaced at the C level between
     the windows: that window fails its check and runs again from its snapshot
@@ -584,7 +584,7 @@ def test_global_path_nonperiodic_potential_bit_exact(with_walls, monkeypatch):
 # ------------------------------------------------------ 6. overlap removal
 def test_overlap_removal_2d_potential_bit_exact():
     """swarm_engine_remove_overlap with the potential set (k_global's
-    steepest descent on a periodic 2-D box, block_global_run_lds), 3 dense
+    steepest descent on a periodic 2-D box, block_env_run), 3 dense
     envs of two species, against sd_run_potential."""
     from gpu_harness import Harness, species_list
 

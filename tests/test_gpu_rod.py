@@ -33,7 +33,7 @@ def _engine(tmp_path, box=50.0, n_envs=1, seed=11, reuse_forces=True, steps_per_
     ureg = UnitRegistry()
     params = MDParams(
         ureg=ureg,
-        box_length=ureg.Quantity(3 * [box], "micrometer"),
+        box_length=ureg.Quantity(list(box) if np.ndim(box) else 3 * [box], "micrometer"),
         temperature=ureg.Quantity(temperature, "kelvin"),
         time_step=ureg.Quantity(time_step, "second"),
         time_slice=ureg.Quantity(time_step * steps_per_slice, "second"),
@@ -147,6 +147,24 @@ def test_rod_run_wraps_the_periodic_boundary(tmp_path):
     _run_against_restatement(eng, 5.0, 3, min_contacts=1)
     img = eng.get_raw_state()["img"][0, :eng.n_particles]
     assert img.min() == 0 and img.max() == 1  # (particles on both sides)
+
+
+def test_rod_run_on_a_grid_of_two_cells(tmp_path):
+    """A 7 x 60 um box: 2 cells across, where both cells of a stencil row are
+    one range and there is no wrap range.  A 7-particle rod of spacing 1
+    (length 7, thickness 1) along y in the middle, 4 swimmers of radius 1 on
+    either side facing it, 0.1 um inside the cutoff (the overlap removal
+    pushes them out, then they press on the rod), E = 2, 3 slices of 20
+    sub-steps."""
+    ureg, eng = _engine(tmp_path, box=[7.0, 60.0, 60.0], n_envs=2)
+    ys = 30.0 + 2.2 * (np.arange(4) - 1.5)
+    pos = [(3.5 - side * 1.4, y) for side in (1.0, -1.0) for y in ys]
+    dirs = [(side, 0.0) for side in (1.0, -1.0) for _ in ys]
+    _add_points(ureg, eng, pos, dirs, 1.0)
+    _add_rod(ureg, eng, (3.5, 30.0), 7.0, 1.0, np.pi / 2, 7, False)
+    assert eng._rod["delta"] == 1.0
+    assert oracle.cell_grid(_restatement(eng)[0], eng.n_particles, 2.0) == (1, 4)
+    _run_against_restatement(eng, 5.0, 3, min_contacts=1)
 
 
 def _large_system():

@@ -5,7 +5,8 @@ What ellipsoids cost per slice: times one RL slice (100 BD sub-steps) of
               radius 0.5, on k_ellipsoid_run<true> (Gay-Berne, cutoff 6);
   spheres     64 envs x 1024 spheres of the same area (radius 0.5 sqrt(3)) in
               the same box, on k_global (SWARMRL_AMD_CLUSTER_PATH=0: the
-              one-workgroup-per-env path the ellipsoid kernel is modelled on),
+              one-workgroup-per-env path whose body, block_env_run, the
+              ellipsoid kernel shares),
 
 at equal area fraction.  The two engines are timed alternately (device events
 around back-to-back slices after a warm-up); one JSON line is printed with the

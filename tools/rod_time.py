@@ -3,8 +3,8 @@ What a rod costs per slice: times one RL slice (100 BD sub-steps) of
 
   rod     64 envs x (50 colloids + a 101-particle rod), on k_rod_run;
   no_rod  the same 64 x 50 colloids without a rod, on k_global
-          (SWARMRL_AMD_CLUSTER_PATH=0: the one-workgroup-per-env path the rod
-          kernel is modelled on),
+          (SWARMRL_AMD_CLUSTER_PATH=0: the one-workgroup-per-env path whose
+          body, block_env_run, the rod kernel shares),
 
 so that their difference is the rod's 101 extra particles, its two barriers
 and its reduction.  The two engines are timed alternately (device events
