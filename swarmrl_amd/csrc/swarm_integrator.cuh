@@ -351,6 +351,13 @@ __device__ __forceinline__ int cell_index(uint32_t qx, uint32_t qy, int lx, int 
   const int cy = ly == 0 ? 0 : (int)(qy >> (32 - ly));
   return (cy << lx) | cx;
 }
+__device__ __forceinline__ int cell_index3(uint32_t qx, uint32_t qy, uint32_t qz, int lx, int ly,
+                                           int lz) {
+  const int cx = lx == 0 ? 0 : (int)(qx >> (32 - lx));
+  const int cy = ly == 0 ? 0 : (int)(qy >> (32 - ly));
+  const int cz = lz == 0 ? 0 : (int)(qz >> (32 - lz));
+  return (((cz << ly) | cy) << lx) | cx;
+}
 
 // Non-periodic boxes (MDParams.periodic = False, espresso.py:270; global
 // path only): the cell of a particle outside the box is the edge cell on its
@@ -794,6 +801,19 @@ __device__ __forceinline__ bool sd_step(const PConst& c, PState& p, int64_t ax, 
   advance(p.qy, p.iy, f2i32(py * c.inv_sx1));
   p.an = p.an + (uint32_t)f2i32(pa * kAngInvScale);
   return any;
+}
+
+// End of a cluster or neighbour-list window for particle i of env e (gi):
+// its largest displacement since the window start, and with half the skin
+// or more a place on the mover list (the exact test of k_check / k_check3).
+__device__ __forceinline__ void window_tail(const Derived* d, const Scratch& sc, int e, int i,
+                                            size_t gi, float dmax2) {
+  const float disp = sqrt_rn(dmax2);
+  sc.disp[gi] = disp;
+  if (!(disp < 0.5f * d->skin)) {
+    const int k = atomicAdd(&sc.nmov[e], 1);
+    if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
+  }
 }
 
 // ------------------------------------------------------- global path
@@ -3597,12 +3617,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     st.vel[M + gi] = vy;
     st.vel[2 * M + gi] = 0.0f;
     st.omega[gi] = om;
-    const float disp = sqrt_rn(dmax2);
-    sc.disp[gi] = disp;
-    if (!(disp < 0.5f * d->skin)) {  // a mover (k_check's exact test)
-      const int k = atomicAdd(&sc.nmov[e], 1);
-      if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
-    }
+    window_tail(d, sc, e, i, gi, dmax2);
     if (st.reuse) {  // the next window's sub-step 0 (the other slot)
       // (fs, tz hold this run's actions unless the window was one sub-step)
       const PrevSlot w = prev_slot(st, par ^ 1);
@@ -3914,12 +3929,7 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
     st.vel[M + gi] = vy;
     st.vel[2 * M + gi] = 0.0f;
     st.omega[gi] = om;
-    const float disp = sqrt_rn(dmax2);
-    sc.disp[gi] = disp;
-    if (!(disp < 0.5f * d->skin)) {  // a mover
-      const int k = atomicAdd(&sc.nmov[e], 1);
-      if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
-    }
+    window_tail(d, sc, e, i, gi, dmax2);
     if (st.reuse) {
       const PrevSlot w = prev_slot(st, par ^ 1);
       w.f[gi] = fs;
@@ -3944,11 +3954,15 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
 // the same.  The 3-D twin is k_build_nlist3 / k_nl_step3.
 // (kNlMax neighbours per colloid; more: the env re-runs)
 
-// Build step 2 (neighbour-list path), grid (ceil(N / 256), E), one thread
-// per cell-sorted entry of k_build_sort: its neighbours into nl[k][gi]
-// (neighbour-major, so the sub-step's reads coalesce).
-__global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict__ d, DevState st,
-                                                      Scratch sc, int lx, int ly) {
+// Build step 2 (neighbour-list path, D = 2 or 3; lz = 0 in 2-D), grid
+// (ceil(N / 256), E), one thread per cell-sorted entry of the build sort: its
+// neighbours into nl[k][gi] (neighbour-major, so the sub-step's reads
+// coalesce).  The stencil is 3 (2-D) or 9 (3-D) rows of (y, z) offsets, each a
+// contiguous x range of the sorted order plus a wrap range at the grid edge.
+template <int D>
+__device__ __forceinline__ void build_nlist_body(const Derived* __restrict__ d, const DevState& st,
+                                                 const Scratch& sc, int lx, int ly, int lz) {
+  constexpr int kR = D == 3 ? 18 : 6;
   __shared__ float nb2[kMaxSpecies * kMaxSpecies];
   for (int k = threadIdx.x; k < kMaxSpecies * kMaxSpecies; k += blockDim.x) nb2[k] = d->nb2[k];
   __syncthreads();
@@ -3956,26 +3970,31 @@ __global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict_
   const int ps = blockIdx.x * blockDim.x + threadIdx.x;
   if (ps >= N) return;
   const size_t M = (size_t)st.m, base = (size_t)e * N;
-  const int ncell = 1 << (lx + ly);
+  const int ncell = 1 << (lx + ly + lz);
   const int32_t* cs = sc.bcstart + (size_t)e * (ncell + 1);
-  const int ncx = 1 << lx, ncy = 1 << ly;
+  const int ncx = 1 << lx, ncy = 1 << ly, ncz = 1 << lz;
   const int loy = ncy >= 3 ? -1 : 0, hiy = ncy >= 3 ? 1 : ncy - 1;
+  const int loz = ncz >= 3 ? -1 : 0, hiz = ncz >= 3 ? 1 : ncz - 1;
   const float sx0 = d->sx[0], sx1 = d->sx[1];
+  [[maybe_unused]] float sx2 = 0.0f;  // (the third axis: read in 3-D only)
+  if constexpr (D == 3) sx2 = d->sx[2];
   const int pk = sc.bsid[base + ps];
   const int i = pk & 0xffffff;
   const uint32_t qx = sc.bsq[base + ps], qy = sc.bsq[M + base + ps];
-  const int c0 = cell_index(qx, qy, lx, ly);
-  const int cx = c0 & (ncx - 1), cy = c0 >> lx;
+  const uint32_t qz = D == 3 ? sc.bsq[2 * M + base + ps] : 0u;
+  const int c0 = cell_index3(qx, qy, qz, lx, ly, lz);
+  const int cx = c0 & (ncx - 1), cy = (c0 >> lx) & (ncy - 1), cz = c0 >> (lx + ly);
   const int xa = ncx >= 3 ? max(cx - 1, 0) : 0;
   const int xb = ncx >= 3 ? min(cx + 1, ncx - 1) : ncx - 1;
   const int xw = ncx >= 3 ? (cx == 0 ? ncx - 1 : (cx == ncx - 1 ? 0 : -1)) : -1;
-  int rb[6], re[6];
+  int rb[kR], re[kR];
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const int oy = loy + (r >> 1), part = r & 1;
-    const bool use = oy <= hiy && (part == 0 || xw >= 0);
-    const int row = ((cy + oy + ncy) & (ncy - 1)) << lx;
-    const int c_lo = row | (part == 0 ? xa : xw), c_hi = row | (part == 0 ? xb : xw);
+  for (int r = 0; r < kR; ++r) {
+    const int row = r >> 1, part = r & 1;
+    const int oy = loy + row % 3, oz = loz + row / 3;
+    const bool use = oy <= hiy && oz <= hiz && (part == 0 || xw >= 0);
+    const int rowc = ((((cz + oz + ncz) & (ncz - 1)) << ly) | ((cy + oy + ncy) & (ncy - 1))) << lx;
+    const int c_lo = rowc | (part == 0 ? xa : xw), c_hi = rowc | (part == 0 ? xb : xw);
     rb[r] = use ? cs[c_lo] : 0;
     re[r] = use ? cs[c_hi + 1] : 0;
   }
@@ -3983,10 +4002,10 @@ __global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict_
   int cnt = 0;
   int32_t* out = sc.nl + base + i;
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
+  for (int r = 0; r < kR; ++r) {
     for (int jj0 = rb[r]; jj0 < re[r]; jj0 += 4) {
       int pk4[4];
-      uint32_t x4[4], y4[4];
+      uint32_t x4[4], y4[4], z4[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int jj = jj0 + u;
@@ -3994,13 +4013,19 @@ __global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict_
         pk4[u] = ok ? sc.bsid[base + jj] : -1;
         x4[u] = ok ? sc.bsq[base + jj] : 0u;
         y4[u] = ok ? sc.bsq[M + base + jj] : 0u;
+        z4[u] = D == 3 && ok ? sc.bsq[2 * M + base + jj] : 0u;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (pk4[u] < 0 || (pk4[u] & 0xffffff) == i) continue;
         const float rx = (float)(int32_t)(x4[u] - qx) * sx0;
         const float ry = (float)(int32_t)(y4[u] - qy) * sx1;
-        if (rx * rx + ry * ry < nb2_row[pk4[u] >> 24]) {
+        float r2 = rx * rx + ry * ry;
+        if constexpr (D == 3) {
+          const float rz = (float)(int32_t)(z4[u] - qz) * sx2;
+          r2 = r2 + rz * rz;
+        }
+        if (r2 < nb2_row[pk4[u] >> 24]) {
           if (cnt < kNlMax) out[(size_t)cnt * M] = pk4[u];
           ++cnt;
         }
@@ -4008,8 +4033,17 @@ __global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict_
     }
   }
   sc.nn[base + i] = min(cnt, kNlMax);
-  reinterpret_cast<uint2*>(sc.qa)[base + i] = make_uint2(qx, qy);  // sub-step 0's read buffer
+  // sub-step 0's read buffer (AoS: uint2 records in 2-D, uint4 in 3-D)
+  if constexpr (D == 3)
+    sc.qa[base + i] = make_uint4(qx, qy, qz, 0u);
+  else
+    reinterpret_cast<uint2*>(sc.qa)[base + i] = make_uint2(qx, qy);
   if (cnt > kNlMax) sc.fallback[e] = 1;  // -> the env re-runs on the global path
+}
+
+__global__ __launch_bounds__(256) void k_build_nlist2(const Derived* __restrict__ d, DevState st,
+                                                      Scratch sc, int lx, int ly) {
+  build_nlist_body<2>(d, st, sc, lx, ly, 0);
 }
 
 // Sub-step s of the 2-D neighbour-list window, one thread per colloid of
@@ -4131,6 +4165,8 @@ __global__ __launch_bounds__(256) void k_nl_step2(const Derived* __restrict__ d,
   st.vel[M + gi] = vy;
   st.vel[2 * M + gi] = 0.0f;
   st.omega[gi] = om;
+  // (window_tail, written out: the call moves this kernel's instructions, and
+  // the one-env dense2d window with them, profiles/r13_step3.txt)
   const float disp = sqrt_rn(dmax2);
   sc.disp[gi] = disp;
   if (!(disp < 0.5f * d->skin)) {  // a mover (k_check's exact test)

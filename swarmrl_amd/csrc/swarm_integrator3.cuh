@@ -2,11 +2,14 @@
 //
 // The reference's default engine dimension is 3 (EspressoMD(n_dims=3),
 // espresso.py:143-152; particles added with rotation about all three axes
-// and no fixed coordinate, espresso.py:415-426).  3-D runs on the global
-// path: one workgroup per env does every sub-step (per sub-step a counting
-// sort into 3-D cells of side >= rc_max, the 27-cell pair search, then the
-// update), so it needs no cluster decomposition.  The 2-D RL workloads of
-// the benchmark use the cluster path (swarm_integrator.cuh).
+// and no fixed coordinate, espresso.py:415-426).  3-D runs windowed like
+// 2-D: the cluster window (k_cluster_run3) in dilute boxes, the
+// neighbour-list window (k_nl_step3) where the rc + skin graph percolates,
+// both checked by k_check3.  The global path (k_global3: one workgroup per
+// env does every sub-step, per sub-step a counting sort into 3-D cells of
+// side >= rc_max and the 27-cell pair search) does the overlap removal and
+// re-runs a window the check rejects.  All three run one sub-step, stated
+// once below (force3, translate3, turn3, velocities3).
 //
 // Orientation is an fp32 unit director.  Per sub-step the rotation vector
 //   phi = tau dt / gamma_r + sqrt(2 kT dt / gamma_r) xi     (lab frame)
@@ -20,14 +23,6 @@
 #include "swarm_integrator.cuh"
 
 namespace swarm {
-
-__device__ __forceinline__ int cell_index3(uint32_t qx, uint32_t qy, uint32_t qz, int lx, int ly,
-                                           int lz) {
-  const int cx = lx == 0 ? 0 : (int)(qx >> (32 - lx));
-  const int cy = ly == 0 ? 0 : (int)(qy >> (32 - ly));
-  const int cz = lz == 0 ? 0 : (int)(qz >> (32 - lz));
-  return (((cz << ly) | cy) << lx) | cx;
-}
 
 __device__ __forceinline__ void pair_force3(float cut2, float sig6, float eps24, float rx,
                                             float ry, float rz, int64_t& ax, int64_t& ay,
@@ -80,6 +75,209 @@ __device__ __forceinline__ void rotate_director(float v[3], float px, float py, 
   v[2] = n2 / nm;
 }
 
+// ------------------------------------------------------ the 3-D sub-step
+// The one fp32 sequence of a 3-D sub-step (oracle: or_bd_run3 / or_sd_run3),
+// shared by the global path (block_global_run3), the cluster wave (run_wave3)
+// and the neighbour-list step (k_nl_step3).  Where the normals come from is
+// the caller's business (step_normals, or StepNoise in the wave); so are the
+// potential lookup and the walls.
+struct PState3 {
+  uint32_t q[3];
+  int32_t im[3];
+  float v[3];  // unit director
+};
+
+// PState3 from / to three [3][M] row sets: the engine's state, or the
+// window-start snapshot.  with_q false: the position rows are left alone
+// (k_nl_step3 keeps the window's positions in its ping-pong buffers).
+// (The order -- director loaded after q / im, q stored last -- is the one
+// under which k_global3 and k_nl_step3 keep their registers,
+// profiles/r13_step3.txt.)
+__device__ __forceinline__ PState3 load_rows3(const uint32_t* q, const int32_t* img,
+                                              const float* dir, size_t M, size_t gi,
+                                              bool with_q = true) {
+  PState3 p;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p.q[a] = with_q ? q[a * M + gi] : 0u;
+    p.im[a] = img[a * M + gi];
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) p.v[a] = dir[a * M + gi];
+  return p;
+}
+__device__ __forceinline__ void store_rows3(const PState3& p, uint32_t* q, int32_t* img, float* dir,
+                                            size_t M, size_t gi, bool with_q = true) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    img[a * M + gi] = p.im[a];
+    dir[a * M + gi] = p.v[a];
+  }
+  if (with_q) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a * M + gi] = p.q[a];
+  }
+}
+__device__ __forceinline__ PState3 load_pstate3(const DevState& st, size_t gi, bool with_q = true) {
+  return load_rows3(st.q, st.img, st.dir3, (size_t)st.m, gi, with_q);
+}
+__device__ __forceinline__ void store_pstate3(const DevState& st, size_t gi, const PState3& p,
+                                              bool with_q = true) {
+  store_rows3(p, st.q, st.img, st.dir3, (size_t)st.m, gi, with_q);
+}
+// The window-start snapshot (k_check3's exact test and re-run).
+__device__ __forceinline__ void snapshot_store3(const Scratch& sc, size_t M, size_t gi,
+                                                const PState3& p) {
+  store_rows3(p, sc.bq, sc.bimg, sc.bdir3, M, gi);
+}
+__device__ __forceinline__ PState3 snapshot_load3(const Scratch& sc, size_t M, size_t gi) {
+  return load_rows3(sc.bq, sc.bimg, sc.bdir3, M, gi);
+}
+
+// A sub-step's actions: swim force, torque and the director the swim force
+// points along.  prev (reuse_forces at sub-step 0): the previous run's, from
+// its slot; else this run's, with the particle's own director v.
+struct Act3 {
+  float fs, tq[3], vs[3];
+};
+__device__ __forceinline__ Act3 load_act3(const DevState& st, const PrevSlot& prv, size_t gi,
+                                          bool prev, const float v[3]) {
+  const size_t M = (size_t)st.m;
+  Act3 a;
+  a.fs = prev ? prv.f[gi] : st.f_swim[gi];
+  a.tq[0] = prev ? prv.txy[gi] : st.torque_xy[gi];
+  a.tq[1] = prev ? prv.txy[M + gi] : st.torque_xy[M + gi];
+  a.tq[2] = prev ? prv.tz[gi] : st.torque_z[gi];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a.vs[k] = prev ? prv.dir3[k * M + gi] : v[k];
+  return a;
+}
+
+// Per-species constants of the update (the last sub-step's velocity
+// constants are read where they are used, velocities3).
+struct PConst3 {
+  float mob_dt, sig_t, rot_dt, sig_r, isx[3];
+  bool noisy;
+};
+__device__ __forceinline__ PConst3 load_pconst3(const Derived* d, int si) {
+  PConst3 c;
+  c.mob_dt = d->mob_dt[si];
+  c.sig_t = d->sig_t[si];
+  c.rot_dt = d->rot_dt[si];
+  c.sig_r = d->sig_r[si];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) c.isx[a] = d->inv_sx[a];
+  c.noisy = d->noisy != 0;
+  return c;
+}
+
+// F = WCA + walls (int64, 2^-24 units) + f_ext (+ field) + f_swim * director,
+// three separately rounded operations per axis.
+__device__ __forceinline__ void force3(const int64_t acc[3], const float fex[3], float fs,
+                                       const float vs[3], float f[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
+    f[a] = f[a] + fex[a];
+    f[a] = f[a] + fs * vs[a];
+  }
+}
+
+// x += F dt / gamma_t + sqrt(2 kT dt / gamma_t) gt
+__device__ __forceinline__ void translate3(const PConst3& c, PState3& p, const float f[3],
+                                           const float gt[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float dq = f[a] * c.mob_dt;
+    if (c.noisy) dq = dq + c.sig_t * gt[a];
+    advance(p.q[a], p.im[a], f2i32(dq * c.isx[a]));
+  }
+}
+
+// The director's turn by phi = tau dt / gamma_r + sqrt(2 kT dt / gamma_r) gr.
+// It does not depend on the forces (run_wave3 computes it while they land).
+__device__ __forceinline__ void turn3(const PConst3& c, float v[3], const float tq[3],
+                                      const float gr[3]) {
+  float ph[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ph[a] = tq[a] * c.rot_dt;
+    if (c.noisy) ph[a] = ph[a] + c.sig_r * gr[a];
+  }
+  rotate_director(v, ph[0], ph[1], ph[2]);
+}
+
+// The last sub-step's velocities (normals3 tags 1 and 3) into st.
+__device__ __forceinline__ void velocities3(const Derived* d, const DevState& st,
+                                            int si, size_t gi, const float f[3], const float tq[3],
+                                            bool noisy, uint32_t k0, uint32_t k1, uint32_t id,
+                                            uint64_t step) {
+  const size_t M = (size_t)st.m;
+  const float inv_gt = d->inv_gt[si], inv_gr = d->inv_gr[si];
+  float vv[3], ww[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    vv[a] = f[a] * inv_gt;
+    ww[a] = tq[a] * inv_gr;
+  }
+  if (noisy) {
+    float gv[3], gw[3];
+    normals3(k0, k1, id, step, 1u, gv);
+    normals3(k0, k1, id, step, 3u, gw);
+    const float sig_v = d->sig_v[si], sig_w = d->sig_w[si];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      vv[a] = vv[a] + sig_v * gv[a];
+      ww[a] = ww[a] + sig_w * gw[a];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) st.vel[a * M + gi] = vv[a];
+  st.omega_xy[gi] = ww[0];
+  st.omega_xy[M + gi] = ww[1];
+  st.omega[gi] = ww[2];
+}
+
+// One Brownian-dynamics sub-step of one particle from its force f (force3):
+// translation, turn, and on the last sub-step the velocities.  gt, gr: the
+// step's translation and rotation normals (read only with noise).
+__device__ __forceinline__ void bd_step3(const Derived* d, const DevState& st,
+                                         const PConst3& c, int si, size_t gi, PState3& p,
+                                         const float f[3], const float tq[3], const float gt[3],
+                                         const float gr[3], uint32_t k0, uint32_t k1, uint32_t id,
+                                         uint64_t step, bool last) {
+  translate3(c, p, f, gt);
+  turn3(c, p.v, tq, gr);
+  if (last) velocities3(d, st, si, gi, f, tq, c.noisy, k0, k1, id, step);
+}
+
+// One steepest-descent step of one particle; returns "anything moved".
+__device__ __forceinline__ bool sd_step3(const Derived* d, PState3& p, const float f[3],
+                                         const float tq[3], float g, float md) {
+  bool any = false;
+  float ph[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (f[a] != 0.0f || tq[a] != 0.0f) any = true;
+    const float dp = fminf(fmaxf(g * f[a], -md), md);
+    ph[a] = fminf(fmaxf(g * tq[a], -md), md);
+    advance(p.q[a], p.im[a], f2i32(dp * d->inv_sx[a]));
+  }
+  rotate_director(p.v, ph[0], ph[1], ph[2]);
+  return any;
+}
+
+// Squared displacement since the window start q0, folded into dmax2.
+__device__ __forceinline__ float disp_update3(const uint32_t q[3], const uint32_t q0[3],
+                                              const float sx[3], float dmax2) {
+  float dd[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) dd[a] = (float)(int32_t)(q[a] - q0[a]) * sx[a];
+  float d2 = dd[0] * dd[0] + dd[1] * dd[1];
+  d2 = d2 + dd[2] * dd[2];
+  return fmaxf(dmax2, d2);
+}
+
 // All sub-steps (or steepest-descent steps) of env e, 3-D, by one
 // workgroup.  cnt: LDS counts of the 2^(lx+ly+lz) cells.
 __device__ void block_global_run3(const Derived* __restrict__ d, const DevState& st,
@@ -100,7 +298,6 @@ __device__ void block_global_run3(const Derived* __restrict__ d, const DevState&
   const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
   const float sx[3] = {d->sx[0], d->sx[1], d->sx[2]};
   const float eps24 = d->eps24;
-  const bool noisy = d->noisy != 0;
   const bool per = d->periodic != 0;  // non-periodic: edge cells, unwrapped differences
   auto cell_of3 = [&](size_t gi) {
     return (((cell_coord(st.q[2 * M + gi], st.img[2 * M + gi], lz, per) << ly) |
@@ -129,16 +326,7 @@ __device__ void block_global_run3(const Derived* __restrict__ d, const DevState&
     int any = 0;
     for (int i = tid; i < N; i += T) {
       const size_t gi = base + i;
-      uint32_t q[3];
-      int32_t im[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        q[a] = st.q[a * M + gi];
-        im[a] = st.img[a * M + gi];
-      }
-      float v[3] = {st.dir3[gi], st.dir3[M + gi], st.dir3[2 * M + gi]};
-      // reuse_forces: sub-step 0 takes the previous run's actions and director
-      const bool first = st.reuse && s == 0 && !sd_mode;
+      PState3 p = load_pstate3(st, gi);
       const int si = st.species[i];
       int64_t acc[3] = {0, 0, 0};
       const int c0 = cell_of3(gi);
@@ -159,15 +347,16 @@ __device__ void block_global_run3(const Derived* __restrict__ d, const DevState&
               if (j == i) continue;
               float rx, ry, rz;
               if (per) {
-                rx = (float)(int32_t)(sc.sqx[base + jj] - q[0]) * sx[0];
-                ry = (float)(int32_t)(sc.sqy[base + jj] - q[1]) * sx[1];
-                rz = (float)(int32_t)(sc.sqz[base + jj] - q[2]) * sx[2];
+                rx = (float)(int32_t)(sc.sqx[base + jj] - p.q[0]) * sx[0];
+                ry = (float)(int32_t)(sc.sqy[base + jj] - p.q[1]) * sx[1];
+                rz = (float)(int32_t)(sc.sqz[base + jj] - p.q[2]) * sx[2];
               } else {
-                rx = pair_disp(sc.sqx[base + jj], sc.simg[base + jj], q[0], im[0], sx[0], false);
-                ry = pair_disp(sc.sqy[base + jj], sc.simg[M + base + jj], q[1], im[1], sx[1],
+                rx = pair_disp(sc.sqx[base + jj], sc.simg[base + jj], p.q[0], p.im[0], sx[0],
                                false);
-                rz = pair_disp(sc.sqz[base + jj], sc.simg[2 * M + base + jj], q[2], im[2], sx[2],
+                ry = pair_disp(sc.sqy[base + jj], sc.simg[M + base + jj], p.q[1], p.im[1], sx[1],
                                false);
+                rz = pair_disp(sc.sqz[base + jj], sc.simg[2 * M + base + jj], p.q[2], p.im[2],
+                               sx[2], false);
               }
               const int pk = si * kMaxSpecies + st.species[j];
               pair_force3(pt->cut2[pk], pt->sig6[pk], eps24, rx, ry, rz, acc[0], acc[1],
@@ -177,87 +366,33 @@ __device__ void block_global_run3(const Derived* __restrict__ d, const DevState&
         }
       }
       if (d->n_walls)
-        wall_forces<3>(d, si, (float)q[0] * sx[0], (float)q[1] * sx[1], (float)q[2] * sx[2],
+        wall_forces<3>(d, si, (float)p.q[0] * sx[0], (float)p.q[1] * sx[1], (float)p.q[2] * sx[2],
                        acc[0], acc[1], acc[2], st.wall_viol);
-      const float fs = first ? prv.f[gi] : st.f_swim[gi];
-      const float tq[3] = {first ? prv.txy[gi] : st.torque_xy[gi],
-                           first ? prv.txy[M + gi] : st.torque_xy[M + gi],
-                           first ? prv.tz[gi] : st.torque_z[gi]};
-      const float vs[3] = {first ? prv.dir3[gi] : v[0], first ? prv.dir3[M + gi] : v[1],
-                           first ? prv.dir3[2 * M + gi] : v[2]};
-      float f[3], dq[3], ph[3];
+      // reuse_forces: sub-step 0 takes the previous run's actions and director
+      const Act3 act = load_act3(st, prv, gi, st.reuse && s == 0 && !sd_mode, p.v);
       float fex[3] = {st.f_ext[gi], st.f_ext[M + gi], st.f_ext[2 * M + gi]};
       if (d->pot.phi) {  // the field at the folded position, every sub-step
         float F[3];
-        potential_force<3>(d->pot, q[0], q[1], q[2], F);
+        potential_force<3>(d->pot, p.q[0], p.q[1], p.q[2], F);
 #pragma unroll
         for (int a = 0; a < 3; ++a) fex[a] = fex[a] + F[a];
       }
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-        f[a] = f[a] + fex[a];
-        f[a] = f[a] + fs * vs[a];
-      }
+      float f[3];
+      force3(acc, fex, act.fs, act.vs, f);
       if (sd_mode) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          if (f[a] != 0.0f || tq[a] != 0.0f) any = 1;
-          const float dp = fminf(fmaxf(g * f[a], -md), md);
-          ph[a] = fminf(fmaxf(g * tq[a], -md), md);
-          advance(q[a], im[a], f2i32(dp * d->inv_sx[a]));
-        }
-        rotate_director(v, ph[0], ph[1], ph[2]);
+        any |= sd_step3(d, p, f, act.tq, g, md) ? 1 : 0;
       } else {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          dq[a] = f[a] * d->mob_dt[si];
-          ph[a] = tq[a] * d->rot_dt[si];
-        }
+        const PConst3 pc = load_pconst3(d, si);
         const uint64_t step = step0 + (uint64_t)s;
-        if (noisy) {
-          float gt[3], gr[3];
+        float gt[3] = {0.0f, 0.0f, 0.0f}, gr[3] = {0.0f, 0.0f, 0.0f};
+        if (pc.noisy) {
           step_normals(k0, k1, (uint32_t)i, step, gt);
           normals3(k0, k1, (uint32_t)i, step, 2u, gr);
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            dq[a] = dq[a] + d->sig_t[si] * gt[a];
-            ph[a] = ph[a] + d->sig_r[si] * gr[a];
-          }
         }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) advance(q[a], im[a], f2i32(dq[a] * d->inv_sx[a]));
-        rotate_director(v, ph[0], ph[1], ph[2]);
-        if (s == n_steps - 1) {
-          float vv[3], ww[3];
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            vv[a] = f[a] * d->inv_gt[si];
-            ww[a] = tq[a] * d->inv_gr[si];
-          }
-          if (noisy) {
-            float gv[3], gw[3];
-            normals3(k0, k1, (uint32_t)i, step, 1u, gv);
-            normals3(k0, k1, (uint32_t)i, step, 3u, gw);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-              vv[a] = vv[a] + d->sig_v[si] * gv[a];
-              ww[a] = ww[a] + d->sig_w[si] * gw[a];
-            }
-          }
-#pragma unroll
-          for (int a = 0; a < 3; ++a) st.vel[a * M + gi] = vv[a];
-          st.omega_xy[gi] = ww[0];
-          st.omega_xy[M + gi] = ww[1];
-          st.omega[gi] = ww[2];
-        }
+        bd_step3(d, st, pc, si, gi, p, f, act.tq, gt, gr, k0, k1, (uint32_t)i, step,
+                 s == n_steps - 1);
       }
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        st.q[a * M + gi] = q[a];
-        st.img[a * M + gi] = im[a];
-        st.dir3[a * M + gi] = v[a];
-      }
+      store_pstate3(st, gi, p);
     }
     if (sd_mode) {
       if (!__syncthreads_or(any)) break;
@@ -544,8 +679,9 @@ __device__ __forceinline__ void pair_fix_sel3(float cut2, float sig6, float eps2
 // in its 64 slots (lane = particle), the wave's neighbour pairs one per lane
 // and pass, positions exchanged through the wave's LDS row, force sums as
 // int64 LDS atomics (order-free, so the bits of block_global_run3).  The
-// update is block_global_run3's sequence: translation from F = WCA + walls +
-// f_ext + f_swim * director, then the Rodrigues turn of the director; the
+// update is the shared sequence (force3, translate3, turn3, velocities3):
+// translation from F = WCA + walls + f_ext + f_swim * director, and the
+// Rodrigues turn of the director; the
 // turn does not depend on the forces, so it is computed while the force sums
 // are in flight.  Normals are drawn here (translation: StepNoise, the
 // step_normals numbers; rotation: normals3 tag 2).
@@ -568,36 +704,13 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
   const bool active = i >= 0;
   const size_t gi = base + (active ? i : 0);
   const int si = kMulti ? st.species[active ? i : 0] : 0;
-  uint32_t q[3];
-  int32_t im[3];
-  float v[3], vs0[3], fex[3], tq[3];
-  float fs;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    q[a] = st.q[a * M + gi];
-    im[a] = st.img[a * M + gi];
-    v[a] = st.dir3[a * M + gi];
-    fex[a] = st.f_ext[a * M + gi];
-  }
-  {
-    // sub-step 0's swim force, torque and swim direction: with
-    // reuse_forces the previous run's (the current ones load after it)
-    const PrevSlot prv = prev_slot(st, par);
-    fs = st.reuse ? prv.f[gi] : st.f_swim[gi];
-    tq[0] = st.reuse ? prv.txy[gi] : st.torque_xy[gi];
-    tq[1] = st.reuse ? prv.txy[M + gi] : st.torque_xy[M + gi];
-    tq[2] = st.reuse ? prv.tz[gi] : st.torque_z[gi];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) vs0[a] = st.reuse ? prv.dir3[a * M + gi] : v[a];
-  }
-  if (active) {  // window-start snapshot (k_check3's exact test and re-run)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      sc.bq[a * M + gi] = q[a];
-      sc.bimg[a * M + gi] = im[a];
-      sc.bdir3[a * M + gi] = v[a];
-    }
-  }
+  PState3 p = load_pstate3(st, gi);
+  const float fex[3] = {st.f_ext[gi], st.f_ext[M + gi], st.f_ext[2 * M + gi]};
+  // sub-step 0's swim force, torque and swim direction: with reuse_forces
+  // the previous run's (the current ones load after it)
+  const PrevSlot prv = prev_slot(st, par);
+  Act3 act = load_act3(st, prv, gi, st.reuse != 0, p.v);
+  if (active) snapshot_store3(sc, M, gi, p);
   const int np = sc.wave_npairs[(size_t)e * sc.wmax + w];
   const int npass = (np + 63) >> 6;
   const uint32_t* pw = sc.pairs + ((size_t)e * sc.wmax + w) * kPairsPerWave;
@@ -607,13 +720,11 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
   lacc_z[lane] = 0ull;
   const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
   const float sx[3] = {d->sx[0], d->sx[1], d->sx[2]};
-  const float isx[3] = {d->inv_sx[0], d->inv_sx[1], d->inv_sx[2]};
   const float eps24 = d->eps24;
-  const bool noisy = d->noisy != 0;
-  const float mob_dt = d->mob_dt[si], sig_t = d->sig_t[si], rot_dt = d->rot_dt[si],
-              sig_r = d->sig_r[si];
+  const PConst3 pc = load_pconst3(d, si);
+  const bool noisy = pc.noisy;
   const float cut2_0 = d->cut2[0], sig6_0 = d->sig6[0];
-  const uint32_t q0[3] = {q[0], q[1], q[2]};
+  const uint32_t q0[3] = {p.q[0], p.q[1], p.q[2]};
   float dmax2 = 0.0f;
   StepNoise noise;
   auto substep = [&](const int s, auto first_t, auto last_t, auto pass_t)
@@ -632,16 +743,16 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
     float fxs[3] = {fex[0], fex[1], fex[2]};
     if constexpr (kPot) {
       float F[3];
-      potential_force<3>(d->pot, q[0], q[1], q[2], F);
+      potential_force<3>(d->pot, p.q[0], p.q[1], p.q[2], F);
 #pragma unroll
       for (int a = 0; a < 3; ++a) fxs[a] = fex[a] + F[a];
     }
     if (kPass > 0) {
-      lpos_w[lane] = make_uint4(q[0], q[1], q[2], 0u);
+      lpos_w[lane] = make_uint4(p.q[0], p.q[1], p.q[2], 0u);
       wave_lds_sync();
-      for (int p = 0; p < (kPass == 1 ? 1 : npass); ++p) {
+      for (int ps = 0; ps < (kPass == 1 ? 1 : npass); ++ps) {
         const uint32_t e_ =
-            p == 0 ? pr0 : (p * 64 + lane < np ? pw[p * 64 + lane] : 0xffffffffu);
+            ps == 0 ? pr0 : (ps * 64 + lane < np ? pw[ps * 64 + lane] : 0xffffffffu);
         const int a = e_ == 0xffffffffu ? lane : (int)(e_ & 63u);
         const int b = e_ == 0xffffffffu ? lane : (int)((e_ >> 6) & 63u);
         const uint4 pa = lpos_w[a], pb = lpos_w[b];
@@ -665,14 +776,8 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
     }
     // the director's turn (independent of the forces) while the sums land
     __builtin_amdgcn_sched_barrier(0);
-    float ph[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      ph[a] = tq[a] * rot_dt;
-      if (noisy) ph[a] = ph[a] + sig_r * gr[a];
-    }
-    float vn[3] = {v[0], v[1], v[2]};
-    rotate_director(vn, ph[0], ph[1], ph[2]);
+    float vn[3] = {p.v[0], p.v[1], p.v[2]};
+    turn3(pc, vn, act.tq, gr);
     __builtin_amdgcn_sched_barrier(0);
     __asm__ volatile("" ::: "memory");
     int64_t acc[3] = {0, 0, 0};
@@ -686,51 +791,16 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
       lacc_z[lane] = 0ull;
     }
     if (kWalls && active)
-      wall_forces<3>(d, si, (float)q[0] * sx[0], (float)q[1] * sx[1], (float)q[2] * sx[2], acc[0],
-                     acc[1], acc[2], st.wall_viol);
+      wall_forces<3>(d, si, (float)p.q[0] * sx[0], (float)p.q[1] * sx[1], (float)p.q[2] * sx[2],
+                     acc[0], acc[1], acc[2], st.wall_viol);
     float f[3];
+    force3(acc, fxs, act.fs, kFirst ? act.vs : p.v, f);
+    translate3(pc, p, f, gt);
+    if (kLast && active)
+      velocities3(d, st, si, gi, f, act.tq, noisy, k0, k1, (uint32_t)i, step);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-      f[a] = f[a] + fxs[a];
-      f[a] = f[a] + fs * (kFirst ? vs0[a] : v[a]);
-      float dq = f[a] * mob_dt;
-      if (noisy) dq = dq + sig_t * gt[a];
-      advance(q[a], im[a], f2i32(dq * isx[a]));
-    }
-    if (kLast && active) {  // velocities of the last sub-step
-      const float inv_gt = d->inv_gt[si], inv_gr = d->inv_gr[si];
-      float vv[3], ww[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        vv[a] = f[a] * inv_gt;
-        ww[a] = tq[a] * inv_gr;
-      }
-      if (noisy) {
-        float gv[3], gw[3];
-        normals3(k0, k1, (uint32_t)i, step, 1u, gv);
-        normals3(k0, k1, (uint32_t)i, step, 3u, gw);
-        const float sig_v = d->sig_v[si], sig_w = d->sig_w[si];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          vv[a] = vv[a] + sig_v * gv[a];
-          ww[a] = ww[a] + sig_w * gw[a];
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 3; ++a) st.vel[a * M + gi] = vv[a];
-      st.omega_xy[gi] = ww[0];
-      st.omega_xy[M + gi] = ww[1];
-      st.omega[gi] = ww[2];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) v[a] = vn[a];
-    float dd[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) dd[a] = (float)(int32_t)(q[a] - q0[a]) * sx[a];
-    float d2 = dd[0] * dd[0] + dd[1] * dd[1];
-    d2 = d2 + dd[2] * dd[2];
-    dmax2 = fmaxf(dmax2, d2);
+    for (int a = 0; a < 3; ++a) p.v[a] = vn[a];
+    dmax2 = disp_update3(p.q, q0, sx, dmax2);
   };
   auto run_steps = [&](auto pass_t) __attribute__((always_inline)) {
     if (n_steps == 1) {
@@ -738,12 +808,7 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
       return;
     }
     substep(0, std::true_type{}, std::false_type{}, pass_t);
-    if (st.reuse) {  // this run's actions from sub-step 1 on
-      fs = st.f_swim[gi];
-      tq[0] = st.torque_xy[gi];
-      tq[1] = st.torque_xy[M + gi];
-      tq[2] = st.torque_z[gi];
-    }
+    if (st.reuse) act = load_act3(st, prv, gi, false, p.v);  // this run's from sub-step 1 on
     int s = 1;
     for (; s < n_steps - 1; ++s) substep(s, std::false_type{}, std::false_type{}, pass_t);
     substep(s, std::false_type{}, std::true_type{}, pass_t);
@@ -755,28 +820,18 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
   else
     run_steps(std::integral_constant<int, 4>{});
   if (active) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      st.q[a * M + gi] = q[a];
-      st.img[a * M + gi] = im[a];
-      st.dir3[a * M + gi] = v[a];
-    }
-    const float disp = sqrt_rn(dmax2);
-    sc.disp[gi] = disp;
-    if (!(disp < 0.5f * d->skin)) {  // a mover (k_check3's exact test)
-      const int k = atomicAdd(&sc.nmov[e], 1);
-      if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
-    }
+    store_pstate3(st, gi, p);
+    window_tail(d, sc, e, i, gi, dmax2);
     if (st.reuse) {  // the next window's sub-step 0 (the other slot)
-      // (fs, tq hold this run's actions unless the window was one sub-step)
+      // (act holds this run's actions unless the window was one sub-step)
       const PrevSlot wsl = prev_slot(st, par ^ 1);
       const bool one = n_steps == 1;
-      wsl.f[gi] = one ? st.f_swim[gi] : fs;
-      wsl.tz[gi] = one ? st.torque_z[gi] : tq[2];
-      wsl.txy[gi] = one ? st.torque_xy[gi] : tq[0];
-      wsl.txy[M + gi] = one ? st.torque_xy[M + gi] : tq[1];
+      wsl.f[gi] = one ? st.f_swim[gi] : act.fs;
+      wsl.tz[gi] = one ? st.torque_z[gi] : act.tq[2];
+      wsl.txy[gi] = one ? st.torque_xy[gi] : act.tq[0];
+      wsl.txy[M + gi] = one ? st.torque_xy[M + gi] : act.tq[1];
 #pragma unroll
-      for (int a = 0; a < 3; ++a) wsl.dir3[a * M + gi] = v[a];
+      for (int a = 0; a < 3; ++a) wsl.dir3[a * M + gi] = p.v[a];
     }
   }
 }
@@ -879,15 +934,8 @@ __global__ __launch_bounds__(1024) void k_check3(const Derived* __restrict__ d, 
     __syncthreads();
   }
   if (flagged_build || misc[1] != 0) {
-    for (int i = tid; i < N && !flagged_build; i += T) {
-      const size_t gi = base + i;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        st.q[a * M + gi] = sc.bq[a * M + gi];
-        st.img[a * M + gi] = sc.bimg[a * M + gi];
-        st.dir3[a * M + gi] = sc.bdir3[a * M + gi];
-      }
-    }
+    for (int i = tid; i < N && !flagged_build; i += T)
+      store_pstate3(st, base + i, snapshot_load3(sc, M, base + i));
     if (tid == 0) sc.fallback[e] = 2;  // diagnostics: env re-run on the global path
     __syncthreads();
     block_global_run3(d, st, sc, e, n_steps, step0, lx, ly, lz, false, 0.0f, 0.0f, cnt, wave_sums,
@@ -908,81 +956,13 @@ __global__ __launch_bounds__(1024) void k_check3(const Derived* __restrict__ d, 
 // then one launch per sub-step with one thread per colloid, reading the
 // positions of sub-step s from one buffer and writing the other (st.q and
 // sc.qalt alternate; k_check3 copies back after an odd window).  Forces,
-// noise and update are block_global_run3's, so the bits are the same.
+// noise and update (bd_step3) are block_global_run3's, so the bits are the
+// same.
 
-// Build step 2 (neighbour-list path), grid (ceil(N / 256), E), one thread
-// per sorted entry: its neighbours into nl[k][gi] (neighbour-major, so the
-// sub-step's reads coalesce).
+// Build step 2 (neighbour-list path): build_nlist_body with the third axis.
 __global__ __launch_bounds__(256) void k_build_nlist3(const Derived* __restrict__ d, DevState st,
                                                       Scratch sc, int lx, int ly, int lz) {
-  constexpr int kR = 18;
-  __shared__ float nb2[kMaxSpecies * kMaxSpecies];
-  for (int k = threadIdx.x; k < kMaxSpecies * kMaxSpecies; k += blockDim.x) nb2[k] = d->nb2[k];
-  __syncthreads();
-  const int e = blockIdx.y, N = st.n;
-  const int ps = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ps >= N) return;
-  const size_t M = (size_t)st.m, base = (size_t)e * N;
-  const int ncell = 1 << (lx + ly + lz);
-  const int32_t* cs = sc.bcstart + (size_t)e * (ncell + 1);
-  const int ncx = 1 << lx, ncy = 1 << ly, ncz = 1 << lz;
-  const int loy = ncy >= 3 ? -1 : 0, hiy = ncy >= 3 ? 1 : ncy - 1;
-  const int loz = ncz >= 3 ? -1 : 0, hiz = ncz >= 3 ? 1 : ncz - 1;
-  const float sx0 = d->sx[0], sx1 = d->sx[1], sx2 = d->sx[2];
-  const int pk = sc.bsid[base + ps];
-  const int i = pk & 0xffffff;
-  const uint32_t qx = sc.bsq[base + ps], qy = sc.bsq[M + base + ps], qz = sc.bsq[2 * M + base + ps];
-  const int c0 = cell_index3(qx, qy, qz, lx, ly, lz);
-  const int cx = c0 & (ncx - 1), cy = (c0 >> lx) & (ncy - 1), cz = c0 >> (lx + ly);
-  const int xa = ncx >= 3 ? max(cx - 1, 0) : 0;
-  const int xb = ncx >= 3 ? min(cx + 1, ncx - 1) : ncx - 1;
-  const int xw = ncx >= 3 ? (cx == 0 ? ncx - 1 : (cx == ncx - 1 ? 0 : -1)) : -1;
-  int rb[kR], re[kR];
-#pragma unroll
-  for (int r = 0; r < kR; ++r) {
-    const int row = r >> 1, part = r & 1;
-    const int oy = loy + row % 3, oz = loz + row / 3;
-    const bool use = oy <= hiy && oz <= hiz && (part == 0 || xw >= 0);
-    const int rowc = ((((cz + oz + ncz) & (ncz - 1)) << ly) | ((cy + oy + ncy) & (ncy - 1))) << lx;
-    const int c_lo = rowc | (part == 0 ? xa : xw), c_hi = rowc | (part == 0 ? xb : xw);
-    rb[r] = use ? cs[c_lo] : 0;
-    re[r] = use ? cs[c_hi + 1] : 0;
-  }
-  const float* nb2_row = nb2 + (pk >> 24) * kMaxSpecies;
-  int cnt = 0;
-  int32_t* out = sc.nl + base + i;
-#pragma unroll
-  for (int r = 0; r < kR; ++r) {
-    for (int jj0 = rb[r]; jj0 < re[r]; jj0 += 4) {
-      int pk4[4];
-      uint32_t x4[4], y4[4], z4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int jj = jj0 + u;
-        const bool ok = jj < re[r];
-        pk4[u] = ok ? sc.bsid[base + jj] : -1;
-        x4[u] = ok ? sc.bsq[base + jj] : 0u;
-        y4[u] = ok ? sc.bsq[M + base + jj] : 0u;
-        z4[u] = ok ? sc.bsq[2 * M + base + jj] : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (pk4[u] < 0 || (pk4[u] & 0xffffff) == i) continue;
-        const float rx = (float)(int32_t)(x4[u] - qx) * sx0;
-        const float ry = (float)(int32_t)(y4[u] - qy) * sx1;
-        const float rz = (float)(int32_t)(z4[u] - qz) * sx2;
-        float r2 = rx * rx + ry * ry;
-        r2 = r2 + rz * rz;
-        if (r2 < nb2_row[pk4[u] >> 24]) {
-          if (cnt < kNlMax) out[(size_t)cnt * M] = pk4[u];
-          ++cnt;
-        }
-      }
-    }
-  }
-  sc.nn[base + i] = min(cnt, kNlMax);
-  sc.qa[base + i] = make_uint4(qx, qy, qz, 0u);  // sub-step 0's read buffer
-  if (cnt > kNlMax) sc.fallback[e] = 1;  // -> the env re-runs on the global path
+  build_nlist_body<3>(d, st, sc, lx, ly, lz);
 }
 
 // Sub-step s of the neighbour-list window, one thread per colloid of every
@@ -1018,43 +998,26 @@ __global__ __launch_bounds__(256) void k_nl_step3(const Derived* __restrict__ d,
   const uint64_t step = ctl[kCtlStep] + (uint64_t)s;
   const int si = kMulti ? st.species[i] : 0;
   const float sx[3] = {d->sx[0], d->sx[1], d->sx[2]};
-  uint32_t q[3], q0[3];
-  int32_t im[3];
-  float v[3];
+  uint32_t q0[3];
   // issue every own load first: one memory latency
   const int nn = sc.nn[gi];
   const uint4 qo = R[gi];
-  q[0] = qo.x;
-  q[1] = qo.y;
-  q[2] = qo.z;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    im[a] = st.img[a * M + gi];
-    v[a] = st.dir3[a * M + gi];
-  }
+  PState3 p = load_pstate3(st, gi, false);  // (the positions: this sub-step's read buffer)
+  p.q[0] = qo.x;
+  p.q[1] = qo.y;
+  p.q[2] = qo.z;
   float dmax2 = 0.0f;
   if (first) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      q0[a] = q[a];
-      sc.bq[a * M + gi] = q[a];
-      sc.bimg[a * M + gi] = im[a];
-      sc.bdir3[a * M + gi] = v[a];
-    }
+    for (int a = 0; a < 3; ++a) q0[a] = p.q[a];
+    snapshot_store3(sc, M, gi, p);
   } else {
 #pragma unroll
     for (int a = 0; a < 3; ++a) q0[a] = sc.bq[a * M + gi];
     dmax2 = sc.disp[gi];
   }
-  const bool reuse0 = st.reuse && first;  // sub-step 0 reuses the previous run's actions
-  const PrevSlot prv = prev_slot(st, par);
-  const float fs = reuse0 ? prv.f[gi] : st.f_swim[gi];
-  const float tq[3] = {reuse0 ? prv.txy[gi] : st.torque_xy[gi],
-                       reuse0 ? prv.txy[M + gi] : st.torque_xy[M + gi],
-                       reuse0 ? prv.tz[gi] : st.torque_z[gi]};
-  float vs[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) vs[a] = reuse0 ? prv.dir3[a * M + gi] : v[a];
+  // sub-step 0 reuses the previous run's actions
+  const Act3 act = load_act3(st, prev_slot(st, par), gi, st.reuse && first, p.v);
   const float eps24 = d->eps24;
   int64_t acc[3] = {0, 0, 0};
   const int32_t* nlp = sc.nl + gi;
@@ -1070,9 +1033,9 @@ __global__ __launch_bounds__(256) void k_nl_step3(const Derived* __restrict__ d,
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       if (pk[u] < 0) continue;
-      const float rx = (float)(int32_t)(qj[u].x - q[0]) * sx[0];
-      const float ry = (float)(int32_t)(qj[u].y - q[1]) * sx[1];
-      const float rz = (float)(int32_t)(qj[u].z - q[2]) * sx[2];
+      const float rx = (float)(int32_t)(qj[u].x - p.q[0]) * sx[0];
+      const float ry = (float)(int32_t)(qj[u].y - p.q[1]) * sx[1];
+      const float rz = (float)(int32_t)(qj[u].z - p.q[2]) * sx[2];
       if (kMulti) {
         const int sp = si * kMaxSpecies + (pk[u] >> 24);
         pair_force3(pt.cut2[sp], pt.sig6[sp], eps24, rx, ry, rz, acc[0], acc[1], acc[2]);
@@ -1082,87 +1045,34 @@ __global__ __launch_bounds__(256) void k_nl_step3(const Derived* __restrict__ d,
     }
   }
   if (kWalls)
-    wall_forces<3>(d, si, (float)q[0] * sx[0], (float)q[1] * sx[1], (float)q[2] * sx[2], acc[0],
-                   acc[1], acc[2], st.wall_viol);
+    wall_forces<3>(d, si, (float)p.q[0] * sx[0], (float)p.q[1] * sx[1], (float)p.q[2] * sx[2],
+                   acc[0], acc[1], acc[2], st.wall_viol);
   const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
-  const bool noisy = d->noisy != 0;
-  float f[3], ph[3];
+  const PConst3 pc = load_pconst3(d, si);
   float gt[3] = {0.0f, 0.0f, 0.0f}, gr[3] = {0.0f, 0.0f, 0.0f};
-  if (noisy) {
+  if (pc.noisy) {
     step_normals(k0, k1, (uint32_t)i, step, gt);
     normals3(k0, k1, (uint32_t)i, step, 2u, gr);
   }
   float fex[3] = {st.f_ext[gi], st.f_ext[M + gi], st.f_ext[2 * M + gi]};
   if (d->pot.phi) {
     float F[3];
-    potential_force<3>(d->pot, q[0], q[1], q[2], F);
+    potential_force<3>(d->pot, p.q[0], p.q[1], p.q[2], F);
 #pragma unroll
     for (int a = 0; a < 3; ++a) fex[a] = fex[a] + F[a];
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    f[a] = i64_to_f32(acc[a]) * 5.9604644775390625e-08f;
-    f[a] = f[a] + fex[a];
-    f[a] = f[a] + fs * vs[a];
-    float dq = f[a] * d->mob_dt[si];
-    ph[a] = tq[a] * d->rot_dt[si];
-    if (noisy) {
-      dq = dq + d->sig_t[si] * gt[a];
-      ph[a] = ph[a] + d->sig_r[si] * gr[a];
-    }
-    advance(q[a], im[a], f2i32(dq * d->inv_sx[a]));
-  }
-  rotate_director(v, ph[0], ph[1], ph[2]);
-  if (last) {  // nobody reads st.q during the window
-#pragma unroll
-    for (int a = 0; a < 3; ++a) st.q[a * M + gi] = q[a];
-  } else {
-    W[gi] = make_uint4(q[0], q[1], q[2], 0u);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    st.img[a * M + gi] = im[a];
-    st.dir3[a * M + gi] = v[a];
-  }
-  float dd[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) dd[a] = (float)(int32_t)(q[a] - q0[a]) * sx[a];
-  float d2 = dd[0] * dd[0] + dd[1] * dd[1];
-  d2 = d2 + dd[2] * dd[2];
-  dmax2 = fmaxf(dmax2, d2);
+  float f[3];
+  force3(acc, fex, act.fs, act.vs, f);
+  bd_step3(d, st, pc, si, gi, p, f, act.tq, gt, gr, k0, k1, (uint32_t)i, step, last);
+  // the last sub-step writes st.q (nobody reads it during the window)
+  if (!last) W[gi] = make_uint4(p.q[0], p.q[1], p.q[2], 0u);
+  store_pstate3(st, gi, p, last);
+  dmax2 = disp_update3(p.q, q0, sx, dmax2);
   if (!last) {
     sc.disp[gi] = dmax2;
     return;
   }
-  {  // velocities of the last sub-step (block_global_run3's sequence)
-    float vv[3], ww[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      vv[a] = f[a] * d->inv_gt[si];
-      ww[a] = tq[a] * d->inv_gr[si];
-    }
-    if (noisy) {
-      float gv[3], gw[3];
-      normals3(k0, k1, (uint32_t)i, step, 1u, gv);
-      normals3(k0, k1, (uint32_t)i, step, 3u, gw);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        vv[a] = vv[a] + d->sig_v[si] * gv[a];
-        ww[a] = ww[a] + d->sig_w[si] * gw[a];
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) st.vel[a * M + gi] = vv[a];
-    st.omega_xy[gi] = ww[0];
-    st.omega_xy[M + gi] = ww[1];
-    st.omega[gi] = ww[2];
-  }
-  const float disp = sqrt_rn(dmax2);
-  sc.disp[gi] = disp;
-  if (!(disp < 0.5f * d->skin)) {  // a mover (k_check3's exact test)
-    const int k = atomicAdd(&sc.nmov[e], 1);
-    if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
-  }
+  window_tail(d, sc, e, i, gi, dmax2);
   if (st.reuse) save_forces(st, gi, par ^ 1);  // this run's actions, the final director
 }
 

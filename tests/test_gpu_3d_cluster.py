@@ -162,6 +162,70 @@ def test_cluster3_matches_global_path(monkeypatch):
     assert out["1"][3][1][0] > 0 and out["0"][3][1][0] == 0  # waves: cluster vs global
 
 
+@pytest.mark.parametrize("kT", [0.0, 1.0239])
+def test_global3_grid_of_two_cells(kT, monkeypatch):
+    """k_global3 (the cluster path switched off) on a grid with two cells on an
+    axis, where block_global_run3's stencil runs over both cells and has no
+    wrap: 2 envs of 24 colloids of radius 1 on a 3 x 4 x 2 lattice in a periodic
+    6 x 40 x 40 um box, columns 2 um apart, also through the periodic boundary;
+    reuse_forces on, chunks of 12 and 1 sub-steps, against oracle.bd_run3, with
+    noise and without (kT = 0: the update's noise-free arms).
+    (More colloids than threads: test_nonperiodic_3d_bit_exact[global-2500].)
+    The oracle runs first: WCA acted (the result differs from free swimming)."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_CLUSTER_PATH", "0")
+    rng = np.random.default_rng(46)
+    E, n, box, radius, species = 2, 24, [6.0, 40.0, 40.0], 1.0, species_list()[:1]
+    g = np.stack(np.meshgrid(np.arange(3), np.arange(4), np.arange(2), indexing="ij"), -1)
+    lattice = np.array([1.0, 12.0, 15.0]) + g.reshape(-1, 3) * np.array([2.0, 2.05, 2.05])
+    sp = np.zeros(n, int)
+    start = [oracle.state3_from_positions(lattice + rng.uniform(-0.1, 0.1, (n, 3)),
+                                          rng.normal(size=(n, 3)), box) for _ in range(E)]
+    op = oracle.make_params(box, 1e-3, kT, 1.0239, 13, species, n_dims=3)
+    free_op = oracle.make_params(box, 1e-3, kT, 0.0, 13, species, n_dims=3)
+    # on the CPU: two cells on x.  The 3-D grid (cell_grid3) takes or_cell_grid's
+    # per-axis rule, floor(log2(6 / 2)) = 1 on x and 4 on y and z, and its cap of
+    # max(n, 64) cells lowers only the largest axis, so it stops at 2 x 4 x 8 = 64
+    # cells with x untouched.
+    assert oracle.cell_grid(op, n, 2 * radius)[0] == 1
+    assert 2 * 4 * 8 <= max(n, 64) < 2 * 8 * 8
+    chunks = []
+    refs = []
+    tracks = [oracle.ReuseForces(s, dims=3) for s in start]
+    free = start[0]
+    free_track = oracle.ReuseForces(free, dims=3)
+    states = list(start)
+    step = 0
+    for nsteps in (12, 1):
+        f = rng.uniform(1.0, 4.0, E * n).astype(np.float32)
+        tq = rng.normal(scale=5.0, size=(3, E * n)).astype(np.float32)
+        chunks.append((nsteps, f, tq))
+        out = []
+        for e in range(E):
+            s = slice(e * n, (e + 1) * n)
+            states[e], v, w = tracks[e].run(op, states[e], sp, f[s], tq[:, s], nsteps, step0=step,
+                                            env=e)
+            out.append((states[e], v, w))
+        free, _, _ = free_track.run(free_op, free, sp, f[:n], tq[:, :n], nsteps, step0=step)
+        refs.append(out)
+        step += nsteps
+    assert not np.array_equal(free["q"], states[0]["q"])  # WCA acted
+    h = Harness(box, 1e-3, kT, 1.0239, 13, species, sp, n_envs=E, n_dims=3, reuse=True)
+    h.upload(start)
+    for (nsteps, f, tq), out in zip(chunks, refs):
+        h.set_actions(f, tq[2])
+        h.set_torque_xy(tq[:2])
+        h.integrate(nsteps)
+        got, vel, om = h.download(), h.velocities(), h.omegas3()
+        for e in range(E):
+            s = slice(e * n, (e + 1) * n)
+            _eq3(got[e], out[e][0])
+            assert np.array_equal(vel[:, s], out[e][1]) and np.array_equal(om[:, s], out[e][2])
+        fb, waves = _stats(h)
+        assert (fb == 0).all() and (waves == 0).all(), (fb, waves)
+
+
 def test_cluster3_reuse_one_substep_window(path3):
     """reuse_forces on the 3-D cluster path, including a window of one
     sub-step (its saved actions are this run's, not the reused ones)."""
@@ -222,6 +286,58 @@ def test_cluster3_rerun_and_big_cluster_bit_exact(path3):
         assert np.array_equal(h.velocities(), v) and np.array_equal(h.omegas3(), w)
         seen.add(int(_stats(h)[0][0]))
     assert 2 in seen  # re-run on the global path
+
+
+def test_cluster3_kt0_window_and_rerun_bit_exact(path3):
+    """kT = 0 (the update's noise-free arms) on the windowed 3-D paths with
+    WCA acting: 256 dimers, partners 1.6 um apart (inside the cutoff r_i + r_j
+    of every species pair but 0.7 + 0.7), on a lattice 8 um apart, so clusters
+    of two.
+    Two windows of 40 sub-steps: with slow swimmers (f = 3) the check passes and
+    the result is k_cluster_run3's or k_nl_step3's alone; with swimmers at
+    f = 400 it fails and the window re-runs inside k_check3.
+    The oracle runs first: in each window the result differs from the
+    free-swimming one (WCA epsilon 0), so a pair force acted."""
+    from gpu_harness import Harness, species_list
+
+    rng = np.random.default_rng(47)
+    k, a = 7, 8.0
+    L = k * a
+    box = [L, L, L]
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), np.arange(k), indexing="ij"), -1)
+    centre = (g.reshape(-1, 3)[:256] + 0.5) * a + rng.uniform(-0.3, 0.3, (256, 3))
+    axis = rng.normal(size=(256, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    pos = np.concatenate([centre - 0.8 * axis, centre + 0.8 * axis])
+    n = len(pos)
+    sp = rng.integers(0, 2, n)
+    start = oracle.state3_from_positions(pos, rng.normal(size=(n, 3)), box)
+    op = oracle.make_params(box, 1e-3, 0.0, 1.0239, 10, species_list(), n_dims=3)
+    free_op = oracle.make_params(box, 1e-3, 0.0, 0.0, 10, species_list(), n_dims=3)
+    chunks, refs = [], []
+    st, free = start, start
+    for w, fmax in enumerate((3.0, 400.0)):
+        f = rng.choice([0.0, fmax], n).astype(np.float32)
+        tq = rng.normal(scale=5.0, size=(3, n)).astype(np.float32)
+        before = st
+        st, v, om = oracle.bd_run3(op, st, sp, f, tq, 40, step0=40 * w)
+        free, _, _ = oracle.bd_run3(free_op, before, sp, f, tq, 40, step0=40 * w)
+        assert not np.array_equal(free["q"], st["q"]), w  # WCA acted in this window
+        chunks.append((f, tq))
+        refs.append((st, v, om))
+    h = Harness(box, 1e-3, 0.0, 1.0239, 10, species_list(), sp, n_dims=3)
+    h.upload([start])
+    codes = []
+    for (f, tq), (ref, v, om) in zip(chunks, refs):
+        h.set_actions(f, tq[2])
+        h.set_torque_xy(tq[:2])
+        h.integrate(40)
+        _eq3(h.download()[0], ref)
+        assert np.array_equal(h.velocities(), v) and np.array_equal(h.omegas3(), om)
+        fb, waves = _stats(h)
+        codes.append(int(fb[0]))
+        assert (waves[0] > 0) == (path3 == "cluster")
+    assert codes == [0, 2], codes  # the first window stood, the second re-ran
 
 
 def test_cluster3_walls_bit_exact(path3):

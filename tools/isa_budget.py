@@ -31,6 +31,13 @@ COMPONENT = {
     "i64x2_to_f32": "bd_update", "i64_to_f32": "bd_update", "i64_to_f32_wide": "bd_update",
     "fits_i32": "bd_update", "wave_all2": "bd_update", "wave_all": "bd_update",
     "rcp_rn": "bd_update", "f2i32": "bd_update", "sqrt_rn": "bd_update",
+    # the 3-D step (swarm_integrator3.cuh)
+    "force3": "bd_update", "translate3": "bd_update", "turn3": "bd_update",
+    "velocities3": "bd_update", "bd_step3": "bd_update", "sd_step3": "bd_update",
+    "rotate_director": "bd_update", "disp_update3": "bd_update", "window_tail": "bd_update",
+    "load_rows3": "bd_update", "store_rows3": "bd_update", "load_pstate3": "bd_update",
+    "store_pstate3": "bd_update", "load_act3": "bd_update", "load_pconst3": "bd_update",
+    "snapshot_store3": "bd_update", "snapshot_load3": "bd_update",
     "wave_lds_sync": "lds_sums",
 }
 
