@@ -253,7 +253,8 @@ typedef struct swarm_rod {
  * runs no cluster windows and declines swarm_engine_prebuild,
  * swarm_engine_defer_build, swarm_engine_prebuild_noise and
  * swarm_engine_hint_defer_check.  2-D periodic boxes without walls; n odd,
- * n <= 255; at most 4096 particles per env; one rod per engine. */
+ * n <= 255; at most 4096 particles per env; one rod per engine; not under
+ * the Langevin thermostat. */
 int swarm_engine_set_rod(swarm_engine_t *e, const swarm_rod_t *rod);
 
 /* Ellipsoidal colloids (espresso.py:802-832 and 420-436): the aspect ratio
@@ -286,11 +287,64 @@ typedef struct swarm_ellipsoids {
  * engine runs no cluster windows and declines swarm_engine_prebuild,
  * swarm_engine_defer_build, swarm_engine_prebuild_noise and
  * swarm_engine_hint_defer_check.  SWARM_EINVAL for a rod, walls, a
- * potential, a non-periodic box, n_dims = 3, aspect_ratio <= 0, a
- * non-positive friction or a cutoff of half the box or more;
+ * potential, the Langevin thermostat, a non-periodic box, n_dims = 3,
+ * aspect_ratio <= 0, a non-positive friction or a cutoff of half the box or
+ * more;
  * SWARM_ECAPACITY when the env's state does not fit the 160 KB of LDS of one
  * workgroup (the message states the particle limit). */
 int swarm_engine_set_ellipsoids(swarm_engine_t *e, const swarm_ellipsoids_t *ell);
+
+/* The Langevin thermostat; replaces integrator.set_vv() +
+ * thermostat.set_langevin of MDParams(thermostat_type="langevin")
+ * (espresso.py:1171-1190).  A setter and not a field of swarm_params_t, whose
+ * layout is fixed.  Call once, before the first swarm_engine_integrate or
+ * swarm_engine_remove_overlap (SWARM_ESTATE afterwards).  From then on every
+ * sub-step is inertial, with swarm_params_t::mass and ::rinertia per species
+ * and the velocities (swarm_device_views_t::vel, ::omega_z; zero at the call)
+ * as integrator state that carries from run to run: per sub-step, with one
+ * force evaluation F (pairs, walls, potential, external and swim force),
+ *   v     += (dt / m) (F + gamma_flow u(x) - (gamma_t + gamma_flow) v
+ *                        + sqrt(24 kT gamma_t / dt) (U - 1/2))     per axis
+ *   omega += (dt / I) (t_z - gamma_r omega + sqrt(24 kT gamma_r / dt) (U - 1/2))
+ *   x += dt v,  theta += dt omega
+ * (velocity Verlet in leapfrog form with the friction at the half-step
+ * velocity; U uniform in [0, 1): the noise has the Gaussian's first two
+ * moments.  Fixed fp32 sequence: swarm_langevin.cuh).  The overlap removal
+ * stays steepest descent and leaves the velocities alone.  Every sub-step
+ * and the overlap removal run in one workgroup per env; the engine runs no
+ * cluster windows and declines swarm_engine_prebuild,
+ * swarm_engine_defer_build, swarm_engine_prebuild_noise and
+ * swarm_engine_hint_defer_check.  Walls, a gridded potential and external
+ * forces act as under the Brownian thermostat.  SWARM_EINVAL for n_dims = 3,
+ * a non-periodic box, a rod, ellipsoids, a mass or rinertia that is not
+ * positive, or a step the explicit friction cannot integrate
+ * (dt gamma_t / m >= 2 or dt gamma_r / I >= 2; the message names the ratio);
+ * SWARM_ECAPACITY when the env's state does not fit the 160 KB of LDS of one
+ * workgroup (the message states the particle limit). */
+int swarm_engine_set_langevin(swarm_engine_t *e);
+
+/* Coupling to a gridded flow field; replaces add_flowfield's
+ * constraints.FlowField (espresso.py:940-993): the drag gamma (u(x) - v) on
+ * every particle, u host fp32 [nx][ny][nz][3] in simulation velocity units
+ * (copied), value [i][j][k] at the cell centre as for
+ * swarm_engine_set_potential_field, periodic and interpolated linearly at
+ * the particle's folded position (2-D: nz = 1, the z component is unused).
+ * In the overlap removal the flow acts with v = 0.  Replaces a previous
+ * field; u = NULL removes it.  The grid rules and their SWARM_EINVAL are
+ * those of swarm_engine_set_potential_field (a 2-D engine stores eight
+ * values per cell); SWARM_EINVAL also on an engine without
+ * swarm_engine_set_langevin, for a negative or non-finite gamma, and when
+ * dt (gamma_t + gamma) / m >= 2.  Moves no particle. */
+int swarm_engine_set_flow_field(swarm_engine_t *e, const float *u, int32_t nx,
+                                int32_t ny, int32_t nz, const double *spacing,
+                                double gamma);
+
+/* The velocities in the engine's own format (host fp32: vel [3][E*N], omega
+ * [E*N]): under the Langevin thermostat they are state, to be restored with
+ * the raw positions.  Download: either pointer may be NULL. */
+int swarm_engine_upload_velocities(swarm_engine_t *e, const float *vel,
+                                   const float *omega);
+int swarm_engine_download_velocities(swarm_engine_t *e, float *vel, float *omega);
 
 /* RotateRod's reward on the device (rod_rotation.py:87-219 with
  * compute_torque_partition_on_rod, colloid_utils.py:29-117), all in fp64:

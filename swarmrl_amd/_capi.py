@@ -318,6 +318,13 @@ _SIGNATURES = {
     "swarm_engine_wall_violations": (ctypes.c_int, [_P, _P]),
     "swarm_engine_set_rod": (ctypes.c_int, [_P, ctypes.POINTER(SwarmRod)]),
     "swarm_engine_set_ellipsoids": (ctypes.c_int, [_P, ctypes.POINTER(SwarmEllipsoids)]),
+    "swarm_engine_set_langevin": (ctypes.c_int, [_P]),
+    "swarm_engine_set_flow_field": (
+        ctypes.c_int,
+        [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_double],
+    ),
+    "swarm_engine_upload_velocities": (ctypes.c_int, [_P, _P, _P]),
+    "swarm_engine_download_velocities": (ctypes.c_int, [_P, _P, _P]),
     "swarm_rod_reward": (
         ctypes.c_int,
         [_P, _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _P],

@@ -43,6 +43,7 @@
 #include "swarm_rnd.cuh"
 #include "swarm_rod.cuh"
 #include "swarm_ellipsoid.cuh"
+#include "swarm_langevin.cuh"
 #include "swarm_observe.cuh"
 #include "swarm_plan.h"
 
@@ -125,9 +126,10 @@ struct swarm_engine {
   int device = 0;
   int n_cus = 0;
   // the cell grids, every path choice and the buffer sizes (swarm_plan.h).
-  // Nothing writes it after swarm_engine_create but swarm_engine_set_rod and
-  // swarm_engine_set_ellipsoids, which take the engine off the cluster path
-  // for good (the latter also widens the global-path grid).
+  // Nothing writes it after swarm_engine_create but swarm_engine_set_rod,
+  // swarm_engine_set_ellipsoids and swarm_engine_set_langevin, which take the
+  // engine off the cluster path for good (the second also widens the
+  // global-path grid).
   swarm::EnginePlan plan;
   DevState st{};
   Scratch sc{};
@@ -212,6 +214,16 @@ struct swarm_engine {
   // (swarm_ellipsoid.cuh); ell_gb: aspect ratio != 1 (Gay-Berne pairs)
   bool has_ell = false, ell_gb = false;
   swarm::EllArgs* d_ell = nullptr;
+  // swarm_engine_set_langevin: every sub-step runs on k_langevin_run
+  // (swarm_langevin.cuh); lv: the host copy of d_lv, gamma_flow: the flow
+  // field's friction (swarm_engine_set_flow_field), d_flow: its records and
+  // their capacity in values
+  bool has_lv = false;
+  swarm::LangevinArgs lv{};
+  swarm::LangevinArgs* d_lv = nullptr;
+  double gamma_flow = 0.0;
+  float* d_flow = nullptr;
+  size_t flow_cap = 0;
   // a sub-step or an overlap-removal step has run
   bool stepped = false;
   // swarm_engine_set_potential_field: the field's device copy (derived.pot.phi
@@ -1562,8 +1574,9 @@ int swarm_engine_wall_violations(swarm_engine_t* e, uint64_t* count) {
   return SWARM_OK;
 }
 
-// An engine that takes a rod or ellipsoids: swarm::plan_no_cluster_windows,
-// and nothing pending of what a window would have used.
+// An engine that takes a rod, ellipsoids or the Langevin thermostat:
+// swarm::plan_no_cluster_windows, and nothing pending of what a window would
+// have used.
 static void no_cluster_windows(swarm_engine_t* e) {
   swarm::plan_no_cluster_windows(e->plan);
   e->defer_hint = false;
@@ -1577,6 +1590,7 @@ int swarm_engine_set_rod(swarm_engine_t* e, const swarm_rod_t* rod) {
   if (const int frc = flush_check(e)) return frc;
   if (e->has_rod) return fail(SWARM_EINVAL, "the engine already has a rod");
   if (e->has_ell) return fail(SWARM_EINVAL, "a rod with ellipsoids is not supported");
+  if (e->has_lv) return fail(SWARM_EINVAL, "a rod under the Langevin thermostat is not supported");
   if (e->params.n_dims != 2) return fail(SWARM_EINVAL, "Rod can only be added in 2d");
   if (!e->params.periodic) return fail(SWARM_EINVAL, "a rod needs a periodic box");
   if (e->derived.n_walls) return fail(SWARM_EINVAL, "a rod with walls is not supported");
@@ -1618,6 +1632,8 @@ int swarm_engine_set_ellipsoids(swarm_engine_t* e, const swarm_ellipsoids_t* ell
   if (e->stepped)
     return fail(SWARM_ESTATE, "ellipsoids must be set before the first integrate or overlap removal");
   if (e->has_ell) return fail(SWARM_EINVAL, "the engine already has ellipsoids");
+  if (e->has_lv)
+    return fail(SWARM_EINVAL, "ellipsoids under the Langevin thermostat are not supported");
   const swarm_params_t& p = e->params;
   if (p.n_dims != 2) return fail(SWARM_EINVAL, "ellipsoids are 2-D only");
   if (!p.periodic) return fail(SWARM_EINVAL, "ellipsoids need a periodic box");
@@ -1706,6 +1722,207 @@ int swarm_rod_reward(swarm_engine_t* e, const int32_t* agent_idx, int32_t n_agen
                      e->d_box, agent_idx, n_agents, hist_ang, ring, count, history, scale,
                      partition, out);
   HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+}  // extern "C"
+
+// ---- the Langevin thermostat and the flow field (swarm_langevin.cuh)
+
+namespace {
+
+// The constants of k_langevin_run from the params and the flow's friction, in
+// fp64 and rounded once; the flow's records stay as they are.  Refuses what
+// the explicit friction cannot integrate: dt (gamma_t + gamma_flow) / m >= 2
+// or dt gamma_r / I >= 2.
+int langevin_derive(const swarm_params_t& p, double gamma_flow, swarm::LangevinArgs* a) {
+  const double kT = p.kT, dt = p.time_step;
+  for (int s = 0; s < p.n_species; ++s) {
+    const double m = p.mass[s], in = p.rinertia[s];
+    if (!(m > 0.0) || !(in > 0.0) || !std::isfinite(m) || !std::isfinite(in))
+      return fail(SWARM_EINVAL, "the Langevin thermostat needs a positive mass and rinertia");
+    const double gt = p.gamma_t[s] + gamma_flow, gr = p.gamma_r[s];
+    const double at = dt * gt / m, ar = dt * gr / in;
+    if (!(at < 2.0))
+      return fail(SWARM_EINVAL, "unstable Langevin step: dt (gamma_t + gamma_flow) / mass = " +
+                                    std::to_string(at) + " for species " + std::to_string(s) +
+                                    ", it must be below 2");
+    if (!(ar < 2.0))
+      return fail(SWARM_EINVAL, "unstable Langevin step: dt gamma_r / rinertia = " +
+                                    std::to_string(ar) + " for species " + std::to_string(s) +
+                                    ", it must be below 2");
+    a->dt_m[s] = (float)(dt / m);
+    a->dt_i[s] = (float)(dt / in);
+    a->gam[s] = (float)gt;
+    a->gam_r[s] = (float)gr;
+    a->sig_t[s] = (float)std::sqrt(24.0 * kT * p.gamma_t[s] / dt);
+    a->sig_r[s] = (float)std::sqrt(24.0 * kT * gr / dt);
+  }
+  for (int ax = 0; ax < 2; ++ax) a->dt_sx[ax] = (float)(dt * kTwo32 / p.box[ax]);
+  a->dt = (float)dt;
+  a->gflow = (float)gamma_flow;
+  return SWARM_OK;
+}
+
+int langevin_upload(swarm_engine* e) {
+  HIP_TRY(hipMemcpyAsync(e->d_lv, &e->lv, sizeof(swarm::LangevinArgs), hipMemcpyHostToDevice,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int swarm_engine_set_langevin(swarm_engine_t* e) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  if (e->stepped)
+    return fail(SWARM_ESTATE,
+                "the thermostat must be set before the first integrate or overlap removal");
+  if (e->has_lv) return fail(SWARM_EINVAL, "the engine already runs the Langevin thermostat");
+  const swarm_params_t& p = e->params;
+  if (p.n_dims != 2) return fail(SWARM_EINVAL, "the Langevin thermostat is 2-D only");
+  if (!p.periodic) return fail(SWARM_EINVAL, "the Langevin thermostat needs a periodic box");
+  if (e->has_rod) return fail(SWARM_EINVAL, "the Langevin thermostat with a rod is not supported");
+  if (e->has_ell)
+    return fail(SWARM_EINVAL, "the Langevin thermostat with ellipsoids is not supported");
+  const size_t fixed = sizeof(swarm::PairTables) + 256;  // (the helpers' own 256 bytes)
+  auto fits = [&](int n, int gx, int gy) {
+    return swarm::env_lds_words(n, 1 << (gx + gy), false, swarm::langevin_tail_words(n)) * 4 +
+               fixed <= kMaxLds;
+  };
+  if (!fits(e->n, e->plan.lxg, e->plan.lyg)) {
+    // 44 bytes of state per particle beside the cell counts and the pair
+    // tables: the most this box admits
+    int limit = e->n, gx = e->plan.lxg, gy = e->plan.lyg;
+    while (limit > 1 && !fits(limit, gx, gy)) {
+      --limit;
+      cell_grid(p, limit, swarm::max_cutoff(p), &gx, &gy);
+    }
+    return fail(SWARM_ECAPACITY, "an engine under the Langevin thermostat holds at most " +
+                                     std::to_string(limit) +
+                                     " particles per env in this box (the 160 KB of LDS of one"
+                                     " workgroup)");
+  }
+  swarm::LangevinArgs a{};
+  if (const int rc = langevin_derive(p, 0.0, &a)) return rc;
+  HIP_TRY(dev_malloc(e, &e->d_lv, sizeof(swarm::LangevinArgs)));
+  e->lv = a;
+  e->gamma_flow = 0.0;
+  if (const int rc = langevin_upload(e)) return rc;
+  // the velocities are integrator state from here on: they start at rest
+  const size_t M = (size_t)e->st.m;
+  HIP_TRY(hipMemsetAsync(e->st.vel, 0, 3 * M * sizeof(float), e->stream));
+  HIP_TRY(hipMemsetAsync(e->st.omega, 0, M * sizeof(float), e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->has_lv = true;
+  no_cluster_windows(e);
+  return SWARM_OK;
+}
+
+int swarm_engine_set_flow_field(swarm_engine_t* e, const float* u, int32_t nx, int32_t ny,
+                                int32_t nz, const double* spacing, double gamma) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  if (!e->has_lv)
+    return fail(SWARM_EINVAL,
+                "a flow field needs the Langevin thermostat (swarm_engine_set_langevin)");
+  if (!u) {  // remove the field (the device copy is kept for a later one)
+    swarm::LangevinArgs a = e->lv;
+    if (const int rc = langevin_derive(e->params, 0.0, &a)) return rc;
+    a.flow = nullptr;
+    a.fn[0] = a.fn[1] = 0;
+    e->lv = a;
+    e->gamma_flow = 0.0;
+    return langevin_upload(e);
+  }
+  if (!spacing) return fail(SWARM_EINVAL, "null spacing");
+  const int32_t n[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a)
+    if (n[a] < 1) return fail(SWARM_EINVAL, "grid counts must be positive");
+  if (nz != 1) return fail(SWARM_EINVAL, "a 2-D engine takes a flow field with nz = 1");
+  const uint64_t count = (uint64_t)nx * (uint64_t)ny;
+  const uint64_t words = 8 * count;  // one record of four corners x two components per cell
+  if (words > 0x7fffffffull) return fail(SWARM_EINVAL, "flow grid too large (32-bit indexing)");
+  for (int a = 0; a < 3; ++a) {
+    const double h = spacing[a], L = e->params.box[a];
+    if (!std::isfinite(h) || !(h > 0.0)) return fail(SWARM_EINVAL, "grid spacing must be positive");
+    if (!(std::fabs(n[a] * h - L) <= 1e-9 * L))
+      return fail(SWARM_EINVAL, "the flow grid must tile the box");
+  }
+  if (!std::isfinite(gamma) || !(gamma >= 0.0))
+    return fail(SWARM_EINVAL, "the flow's friction must be finite and not negative");
+  for (uint64_t k = 0; k < 3 * count; ++k)
+    if (!std::isfinite(u[k])) return fail(SWARM_EINVAL, "non-finite flow value");
+  swarm::LangevinArgs a = e->lv;
+  if (const int rc = langevin_derive(e->params, gamma, &a)) return rc;
+  // u[i][j][0][c], c = 0, 1 (the z component is unused in 2-D)
+  std::vector<float> rec((size_t)words);
+  for (int32_t i = 0; i < nx; ++i) {
+    const size_t r0 = (size_t)i * ny, r1 = (size_t)((i + 1) % nx) * ny;
+    for (int32_t j = 0; j < ny; ++j) {
+      const size_t j1 = (size_t)((j + 1) % ny);
+      float* o = &rec[8 * (r0 + j)];
+      for (int c = 0; c < 2; ++c) {
+        o[4 * c + 0] = u[3 * (r0 + j) + c];
+        o[4 * c + 1] = u[3 * (r1 + j) + c];
+        o[4 * c + 2] = u[3 * (r0 + j1) + c];
+        o[4 * c + 3] = u[3 * (r1 + j1) + c];
+      }
+    }
+  }
+  if (words > e->flow_cap) {
+    // the new copy first: a failed allocation leaves the old field in place
+    float* v = nullptr;
+    HIP_TRY(dev_malloc(e, &v, words * sizeof(float)));
+    if (e->d_flow) {
+      // no kernel may find the old copy once it is freed: the device's
+      // descriptor is cleared first, and the stream drained of its readers
+      e->lv.flow = nullptr;
+      int rc = langevin_upload(e);
+      if (rc == SWARM_OK && dev_free(e, &e->d_flow) != hipSuccess)
+        rc = fail(SWARM_EDEVICE, "flow field: hipFree failed");
+      if (rc) {
+        (void)dev_free(e, &v);
+        if (!e->d_flow) e->flow_cap = 0;
+        return rc;
+      }
+    }
+    e->d_flow = v;
+    e->flow_cap = (size_t)words;
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_flow, rec.data(), words * sizeof(float), hipMemcpyHostToDevice,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // (rec is a local)
+  a.flow = e->d_flow;
+  a.fn[0] = nx;
+  a.fn[1] = ny;
+  e->lv = a;
+  e->gamma_flow = gamma;
+  return langevin_upload(e);
+}
+
+int swarm_engine_upload_velocities(swarm_engine_t* e, const float* vel, const float* omega) {
+  if (!e || !vel || !omega) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  const size_t M = (size_t)e->st.m;
+  HIP_TRY(hipMemcpyAsync(e->st.vel, vel, 3 * M * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->st.omega, omega, M * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+int swarm_engine_download_velocities(swarm_engine_t* e, float* vel, float* omega) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  const size_t M = (size_t)e->st.m;
+  if (vel)
+    HIP_TRY(hipMemcpyAsync(vel, e->st.vel, 3 * M * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (omega)
+    HIP_TRY(hipMemcpyAsync(omega, e->st.omega, M * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return SWARM_OK;
 }
 

@@ -109,11 +109,12 @@ void allow_engine_lds(int device) {
   allow(&k_policy_cbuild<4, 4, 4>);
   // (last: every kernel above keeps its place in the code object)
   swarm_select::each_bools<1>([&](auto gb) { allow(&swarm::k_ellipsoid_run<gb>); });
+  allow(&swarm::k_langevin_run);
   (void)hipGetLastError();
   done.push_back(device);
 }
 
-// ---- the global path, the rod, the ellipsoids, the noise table
+// ---- the global path, the rod, the ellipsoids, the Langevin thermostat, the noise table
 
 int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) {
   const swarm::EnginePlan& pl = e->plan;
@@ -141,6 +142,15 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
                          e->d_derived, e->st, e->d_ell, n_steps, e->d_step, e->d_arrive, pl.lxg,
                          pl.lyg, sd_mode, g, md);
     }, e->ell_gb);
+    HIP_TRY(hipGetLastError());
+    return SWARM_OK;
+  }
+  if (e->has_lv) {
+    hipLaunchKernelGGL(swarm::k_langevin_run, dim3(e->n_envs), dim3(1024),
+                       swarm::env_lds_words(e->n, 1 << (pl.lxg + pl.lyg), false,
+                                            swarm::langevin_tail_words(e->n)) * 4, e->stream,
+                       e->d_derived, e->st, e->d_lv, n_steps, e->d_step, e->d_arrive, pl.lxg,
+                       pl.lyg, sd_mode, g, md);
     HIP_TRY(hipGetLastError());
     return SWARM_OK;
   }

@@ -1,6 +1,6 @@
 // swarm_env_block.cuh -- one workgroup per env, the env's state resident in
-// LDS: the sub-step loop that k_global, the re-run inside k_check, k_rod_run
-// and k_ellipsoid_run share.  Per sub-step a counting sort into cells of side
+// LDS: the sub-step loop that k_global, the re-run inside k_check, k_rod_run,
+// k_ellipsoid_run and k_langevin_run share.  Per sub-step a counting sort into cells of side
 // >= the cutoff, then every particle, in sorted order, sums its pairs over the
 // 3 x 3 cells (int64 at 2^-24: independent of visiting order) and is advanced.
 // Periodic 2-D boxes of up to kGlobalCH * 1024 particles.
@@ -8,7 +8,8 @@
 // What differs between the kernels is a path: a small struct of
 // __forceinline__ hooks (EnvPathBase has the plain colloid's).  PlainEnvPath
 // (walls, potential) follows the body in swarm_integrator.cuh, RodEnvPath is
-// in swarm_rod.cuh and EllEnvPath in swarm_ellipsoid.cuh.
+// in swarm_rod.cuh, EllEnvPath in swarm_ellipsoid.cuh and LangevinEnvPath in
+// swarm_langevin.cuh.
 //
 // Part of swarm_integrator.cuh (included there, after sd_step and bd_step):
 // not a header to include on its own.

@@ -174,7 +174,8 @@ struct EnginePlan {
 };
 
 // An engine whose every sub-step runs on one workgroup per env (a rod,
-// ellipsoids): no cluster windows, and none of what prepares or checks them.
+// ellipsoids, the Langevin thermostat): no cluster windows, and none of what
+// prepares or checks them.
 // The one rewrite of a plan after creation.
 inline void plan_no_cluster_windows(EnginePlan& pl) {
   pl.cluster_path = false;

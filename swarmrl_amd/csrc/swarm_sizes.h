@@ -60,6 +60,10 @@ SWARM_HD inline size_t env_lds_words(int n, int ncell, bool dirs, size_t tail_wo
   return 16 + (size_t)ncell + 1 + 1 + (dirs ? 10 : 8) * (size_t)n + tail_words;
 }
 
+// What k_langevin_run (swarm_langevin.cuh) keeps after the particle state: the
+// env's velocities v_x[n], v_y[n], omega[n].
+SWARM_HD inline size_t langevin_tail_words(int n) { return 3 * (size_t)n; }
+
 // LDS words the LDS-resident global path needs after the cell counts (with
 // one spare word, which the capacity thresholds below have always counted),
 // 0 when it does not apply (3-D, or more than kGlobalCH particles per thread

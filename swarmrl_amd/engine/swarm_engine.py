@@ -10,8 +10,11 @@ library through the C ABI of include/swarmrl_amd.h.  There is no CPU
 fallback: without a HIP device the engine raises.
 
 Scope of this build: 2-D, periodic box, spheres (WCA) or
-ellipsoids (Gay-Berne, per-axis friction), Brownian thermostat, one rigid rod
-(add_rod).  LB and the Langevin integrator raise NotImplementedError.
+ellipsoids (Gay-Berne, per-axis friction), one rigid rod (add_rod), under the
+Brownian thermostat; under thermostat_type "langevin" spheres in a 2-D
+periodic box with walls, a gridded potential and a flow field (add_flowfield).
+LB raises NotImplementedError, as do the Langevin thermostat in 3-D, in a
+non-periodic box, with a rod or with ellipsoids.
 """
 
 from __future__ import annotations
@@ -303,6 +306,8 @@ class SwarmEngine(Engine):
         self._rod = None  # add_rod: first index, particles, bead spacing, fixed, type
         # add_external_potential: {"phi": fp64 (nx, ny, nz), "h": fp64 (3,)}, simulation units
         self._potential = None
+        # add_flowfield: {"u": fp64 (nx, ny, nz, 3), "h": fp64 (3,), "gamma": float}
+        self._flow = None
         self._native: _NativeEngine = None
         self._host_cache = None
         self._view = None
@@ -665,6 +670,7 @@ class SwarmEngine(Engine):
             "fixed": bool(fixed), "type": int(rod_particle_type),
         }
         self._validate_rod(rod)
+        self._validate_langevin(rod=True)
         self._rod = rod
         if point_dist > 2 * partcl_radius:
             logger.warning(
@@ -756,6 +762,24 @@ class SwarmEngine(Engine):
         # (the particle limit of the kernel's LDS depends on the box and the
         # cutoff: swarm_engine_set_ellipsoids states it)
 
+    def _validate_langevin(self, rod=False):
+        """What the Langevin path cannot run: refused at the first integrate,
+        before the engine is created, and when a rod is added (rod=True).
+        Ellipsoids and per-axis friction: _validate_ellipsoids."""
+        if self.params.thermostat_type != "langevin":
+            return
+        if self.n_dims != 2:
+            # rotation with inertia needs a body-frame angular velocity
+            raise NotImplementedError(
+                "the Langevin thermostat is implemented for 2d engines only")
+        if not self.params.periodic:
+            raise NotImplementedError(
+                "the Langevin thermostat in a non-periodic box is not implemented")
+        if rod or self._rod is not None:
+            raise NotImplementedError(
+                "a rod under the Langevin thermostat is not implemented")
+        self._validate_ellipsoids()
+
     def add_const_force_to_colloids(self, force: Quantity, type: int):
         """Constant external force on every colloid of a type (espresso.py:834-851).
         The force is kept per type and laid out per colloid when it is handed
@@ -845,10 +869,9 @@ class SwarmEngine(Engine):
                               boundary_mask: np.array = None, ext_force_density: Quantity = None,
                               use_GPU: bool = False):
         """espresso.py:853-938: the reference refuses it with the Brownian
-        thermostat (espresso.py:887-891), the only one this engine runs.  With
-        thermostat_type "langevin", where the reference goes on to build the
-        fluid, this raises NotImplementedError (as the first integrate does
-        for that thermostat)."""
+        thermostat (espresso.py:887-891).  With thermostat_type "langevin",
+        where the reference goes on to build the fluid, this raises
+        NotImplementedError."""
         if not self.params.thermostat_type == "langevin":
             raise RuntimeError(
                 "Coupling to lattice boltzmann does not work with a Brownian"
@@ -858,16 +881,73 @@ class SwarmEngine(Engine):
 
     def add_flowfield(self, flowfield: Quantity, friction_coeff: Quantity,
                       grid_spacings: Quantity):
-        """espresso.py:940-993: refused with the Brownian thermostat as the
-        reference does (espresso.py:967-971).  With thermostat_type
-        "langevin", where the reference adds the FlowField constraint, this
-        raises NotImplementedError."""
+        """
+        Coupling to a precomputed flow (espresso.py:940-993): flowfield has
+        shape (n_cells_x, n_cells_y, n_cells_z, 3) and units of velocity,
+        value [i, j, k, :] at the cell centre ((i + .5) hx, (j + .5) hy,
+        (k + .5) hz); friction_coeff is one scalar in units of mass / time for
+        every particle.  Every particle feels gamma (u(x) - v), u interpolated
+        linearly and periodically at the folded position; in the overlap
+        removal with v = 0.  Refused with the Brownian thermostat as the
+        reference does (espresso.py:967-971).  2-D: one cell along z
+        (grid_spacings[2] = box_l), the z component is unused.  The grid has
+        to tile the box.  A second call with the same grid and friction adds
+        to the field (ESPResSo sums its constraints).
+        """
         if not self.params.thermostat_type == "langevin":
             raise RuntimeError(
                 "Coupling to a flowfield does not work with a Brownian thermostat. Use"
                 " 'langevin'."
             )
-        raise NotImplementedError("flow field coupling is not implemented in this build")
+        flow = np.asarray(flowfield.m_as("sim_velocity"), dtype=float)
+        gamma = np.asarray(friction_coeff.m_as("sim_mass/sim_time"), dtype=float)
+        agrids = np.asarray(grid_spacings.m_as("sim_length"), dtype=float)
+        if not flow.ndim == 4:
+            raise ValueError(
+                "flowfield must have shape (n_cells_x, n_cells_y, n_cells_z, 3)"
+            )
+        if not len(grid_spacings) == 3:
+            raise ValueError("Grid spacings must have length of 3")
+        self._check_already_initialised()
+        if flow.shape[3] != 3 or flow.size == 0 or not np.all(np.isfinite(flow)):
+            raise ValueError("flowfield must hold three finite components per cell")
+        if gamma.size != 1 or not np.isfinite(gamma).all() or not gamma.reshape(-1)[0] >= 0.0:
+            raise ValueError("friction_coeff must be one non-negative scalar")
+        gamma = float(gamma.reshape(-1)[0])
+        if not (np.all(np.isfinite(agrids)) and np.all(agrids > 0)):
+            raise ValueError("Grid spacings must be positive")
+        if self.n_dims == 2 and flow.shape[2] != 1:
+            raise ValueError(
+                "a 2d simulation takes a flowfield with one cell in z"
+                f" (choose grid_spacings[2]=box_l). You gave shape {flow.shape}"
+            )
+        extent = np.asarray(flow.shape[:3], dtype=float) * agrids
+        if np.any(np.abs(extent - self._box) > 1e-9 * self._box):
+            raise ValueError(
+                f"the flowfield grid must tile the box: {flow.shape[:3]} cells of {agrids}"
+                f" span {extent}, the box is {self._box}"
+            )
+        # (the 2-D device copy holds the four corners x two components of every cell)
+        if flow.shape[0] * flow.shape[1] * 8 > 2**31 - 1:
+            raise ValueError("the flowfield grid is too large")
+        if self._flow is not None:
+            old = self._flow
+            if (old["u"].shape != flow.shape or not np.array_equal(old["h"], agrids)
+                    or old["gamma"] != gamma):
+                raise NotImplementedError(
+                    "flow fields on different grids or with different friction coefficients"
+                    " are not implemented")
+            old["u"] = old["u"] + flow
+            return
+        self._flow = {"u": flow.copy(), "h": agrids.copy(), "gamma": gamma}
+        self.system.constraints.append(self._flow)
+
+    def _upload_flow(self):
+        u = np.ascontiguousarray(self._flow["u"], dtype=np.float32)
+        h = np.ascontiguousarray(self._flow["h"], dtype=np.float64)
+        nx, ny, nz = u.shape[:3]
+        self._native.call("swarm_engine_set_flow_field", u.ctypes.data, int(nx), int(ny), int(nz),
+                          h.ctypes.data, float(self._flow["gamma"]))
 
     def add_external_potential(self, potential: Quantity, grid_spacings: Quantity):
         """
@@ -962,6 +1042,7 @@ class SwarmEngine(Engine):
 
     def _setup_interactions(self):
         """WCA between every pair of types (espresso.py:802-832) + engine creation."""
+        self._validate_langevin()  # (host logic: before a device is asked for)
         _capi.require_gpu()
         if self.n_particles == 0:
             raise ValueError("no colloids were added to the engine")
@@ -970,8 +1051,6 @@ class SwarmEngine(Engine):
             raise ValueError("All particles in the system must have the same aspect ratio.")
         if self.params.thermostat_type not in ["brownian", "langevin"]:
             raise ValueError("integrator_type must be one of ['brownian', 'langevin']")
-        if self.params.thermostat_type == "langevin":
-            raise NotImplementedError("the Langevin integrator is not implemented in this build")
 
         p = _capi.SwarmParams()
         p.n_dims = self.n_dims
@@ -990,6 +1069,8 @@ class SwarmEngine(Engine):
         self._params_c = p
         self._native = _NativeEngine(p, self.n_envs, np.asarray(self._species_of))
         self._native.bind_stream()
+        if self.params.thermostat_type == "langevin":  # espresso.py:1171-1190
+            self._native.call("swarm_engine_set_langevin")
 
         pos = np.ascontiguousarray(np.stack([np.stack(v) for v in self._pos]), dtype=float)
         dirs = np.ascontiguousarray(np.stack([np.stack(v) for v in self._dir]), dtype=float)
@@ -1009,6 +1090,8 @@ class SwarmEngine(Engine):
                               len(self._walls))
         if self._potential is not None:  # before the overlap removal: a constraint acts there
             self._upload_potential()
+        if self._flow is not None:  # likewise
+            self._upload_flow()
 
         if self._rod is not None:
             rod = _capi.SwarmRod()
@@ -1458,8 +1541,10 @@ class SwarmEngine(Engine):
         return self.ureg
 
     # ---------------------------------------------------- raw state (tests)
-    def get_raw_state(self) -> dict:
-        """Exact engine state: q/img uint32/int32 [3, E*N], ang uint32 [E*N]."""
+    def get_raw_state(self, velocities: bool = False) -> dict:
+        """Exact engine state: q/img uint32/int32 [3, E*N], ang uint32 [E*N];
+        velocities: also vel fp32 [3, E*N] and omega fp32 [E*N] (integrator
+        state under the Langevin thermostat)."""
         M = self.n_envs * self.n_particles
         q = np.zeros((3, M), dtype=np.uint32)
         img = np.zeros((3, M), dtype=np.int32)
@@ -1468,14 +1553,33 @@ class SwarmEngine(Engine):
         self._native.call(
             "swarm_engine_download_raw", q.ctypes.data, img.ctypes.data, ang.ctypes.data
         )
-        return {"q": q, "img": img, "ang": ang}
+        out = {"q": q, "img": img, "ang": ang}
+        if velocities:
+            vel = np.zeros((3, M), dtype=np.float32)
+            omega = np.zeros(M, dtype=np.float32)
+            self._native.call("swarm_engine_download_velocities", vel.ctypes.data,
+                              omega.ctypes.data)
+            out.update({"vel": vel, "omega": omega})
+        return out
 
-    def set_raw_state(self, q: np.ndarray, img: np.ndarray, ang: np.ndarray):
+    def set_raw_state(self, q: np.ndarray, img: np.ndarray, ang: np.ndarray,
+                      vel: np.ndarray = None, omega: np.ndarray = None):
+        """vel and omega (both or neither): the velocities with the state."""
         q = np.ascontiguousarray(q, dtype=np.uint32)
         img = np.ascontiguousarray(img, dtype=np.int32)
         ang = np.ascontiguousarray(ang, dtype=np.uint32)
+        if (vel is None) != (omega is None):
+            raise ValueError("give vel and omega together")
         self._native.bind_stream()
         self._native.call("swarm_engine_upload_raw", q.ctypes.data, img.ctypes.data, ang.ctypes.data)
+        if vel is not None:
+            M = self.n_envs * self.n_particles
+            vel = np.ascontiguousarray(vel, dtype=np.float32)
+            omega = np.ascontiguousarray(omega, dtype=np.float32)
+            if vel.shape != (3, M) or omega.shape != (M,):
+                raise ValueError(f"vel must have shape (3, {M}) and omega ({M},)")
+            self._native.call("swarm_engine_upload_velocities", vel.ctypes.data,
+                              omega.ctypes.data)
         self._host_cache = None
 
     def window_stats(self) -> dict:
