@@ -369,6 +369,65 @@ int swarm_rod_reward(swarm_engine_t *e, const int32_t *agent_idx, int32_t n_agen
 int swarm_engine_remove_overlap(swarm_engine_t *e, int32_t n_steps,
                                 double gamma, double max_displacement);
 
+/* Both reuse_forces slots as the engine holds them (host; any pointer may be
+ * NULL): f_prev, tz_prev fp32 [2][E*N], ang_prev uint32 [2][E*N], and on a
+ * 3-D engine dir3_prev fp32 [2][3][E*N] and txy_prev fp32 [2][2][E*N] (left
+ * alone in 2-D).  Slot p is read by the windows whose device window counter
+ * has parity p.  For tests and diagnostics; synchronous. */
+int swarm_engine_download_reuse_slots(swarm_engine_t *e, float *f_prev,
+                                      float *tz_prev, uint32_t *ang_prev,
+                                      float *dir3_prev, float *txy_prev);
+
+/* A placement group of the reset plan: particles [first, first + count) of
+ * every env are drawn uniformly in the disc (2-D) or ball (3-D) of this
+ * radius round this centre (add_colloids, espresso.py:459-544), each with a
+ * uniform director. */
+typedef struct swarm_reset_group {
+  int32_t first;
+  int32_t count;
+  double centre[3];
+  double radius;
+} swarm_reset_group_t;
+
+/* What swarm_engine_reset_envs puts a listed env back to.  pos and director:
+ * host fp64 [E][N][3] with the meaning they have for
+ * swarm_engine_upload_state (copied, converted by its rules and kept on the
+ * device): the home state, which every particle outside the groups and every
+ * particle of a group of radius 0 returns to.  groups: n_groups disjoint
+ * particle ranges (NULL with n_groups = 0: every particle goes home).
+ * Replaces a previous plan.  Moves no particle.  SWARM_EINVAL for
+ * overlapping or out-of-range groups, a negative or non-finite radius or
+ * centre, and a radius above half the shortest box edge. */
+int swarm_engine_set_reset_plan(swarm_engine_t *e, const double *pos,
+                                const double *director,
+                                const swarm_reset_group_t *groups,
+                                int32_t n_groups);
+
+/* Episodic reset in place: the envs with env_mask[env] != 0 (host uint8 [E];
+ * NULL: every env) are put back to a fresh random start on the device; the
+ * engine, its buffers and captured graphs stay.  Per listed env:
+ *   - grouped particles are drawn anew (Philox key (seed lo, seed hi ^ env),
+ *     counter (particle, reset ordinal lo, hi, 0x30 + block); the ordinal
+ *     counts this engine's non-empty reset calls from 0; DESIGN.md section 3
+ *     states the fp32 sequence), the others return to their home state;
+ *   - velocities, angular velocities, the actions (f_swim, torque_z,
+ *     torque_xy; written through a binding of swarm_engine_set_actions with
+ *     on_device = 2 as well) are zeroed and both reuse_forces slots are as on
+ *     a fresh engine after its overlap removal;
+ *   - sd_steps steps of the overlap removal run on the listed envs alone
+ *     (sd_steps = 0: placement only).
+ * An env that is not listed is not touched by a single store.  The device
+ * step counter, the window counter and the wall-violation count go on: the
+ * noise of the next run continues the engine's stream.  Flushes a pending
+ * check and discards a pending build like swarm_engine_remove_overlap.
+ * Asynchronous on the engine stream apart from the copy of the env list; not
+ * to be captured into a graph.  An empty mask is a no-op.  SWARM_ESTATE
+ * without a reset plan; SWARM_EINVAL on an engine with a rod, ellipsoids or
+ * the Langevin thermostat, and for sd_steps < 0. */
+int swarm_engine_reset_envs(swarm_engine_t *e, const uint8_t *env_mask,
+                            int32_t sd_steps, double gamma,
+                            double max_displacement);
+
 /* n_steps Brownian-dynamics sub-steps with WCA pair forces; replaces
  * system.integrator.run(k, reuse_forces=True, recalc_forces=False)
  * (espresso.py:1304-1306).  Asynchronous on the engine stream. */

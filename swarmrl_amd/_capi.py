@@ -108,6 +108,17 @@ class SwarmEllipsoids(ctypes.Structure):
     ]
 
 
+class SwarmResetGroup(ctypes.Structure):
+    """swarm_reset_group_t: particles [first, first + count) of every env, the
+    disc (ball) they are placed in."""
+    _fields_ = [
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("centre", ctypes.c_double * 3),
+        ("radius", ctypes.c_double),
+    ]
+
+
 class SwarmVisionParams(ctypes.Structure):
     _fields_ = [
         ("vision_range", ctypes.c_float),
@@ -156,6 +167,12 @@ _SIGNATURES = {
     "swarm_engine_remove_overlap": (
         ctypes.c_int,
         [_P, ctypes.c_int32, ctypes.c_double, ctypes.c_double],
+    ),
+    "swarm_engine_download_reuse_slots": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "swarm_engine_set_reset_plan": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    "swarm_engine_reset_envs": (
+        ctypes.c_int,
+        [_P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_double],
     ),
     "swarm_engine_integrate": (ctypes.c_int, [_P, ctypes.c_int32]),
     "swarm_engine_prebuild": (ctypes.c_int, [_P, _P, ctypes.c_int32]),

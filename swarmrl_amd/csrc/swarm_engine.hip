@@ -45,6 +45,7 @@
 #include "swarm_ellipsoid.cuh"
 #include "swarm_langevin.cuh"
 #include "swarm_observe.cuh"
+#include "swarm_reset.cuh"
 #include "swarm_plan.h"
 
 namespace {
@@ -230,6 +231,19 @@ struct swarm_engine {
   // points at it while a field is set) and its capacity in values
   float* d_pot = nullptr;
   size_t pot_cap = 0;
+  // swarm_engine_set_reset_plan: the home state, each particle's placement
+  // group (-1: home) and the groups; d_reset_envs: the env list of a
+  // swarm_engine_reset_envs call; reset_ordinal: the non-empty calls so far
+  bool has_reset_plan = false;
+  uint32_t* d_home_q = nullptr;
+  int32_t* d_home_img = nullptr;
+  uint32_t* d_home_ang = nullptr;
+  float* d_home_dir3 = nullptr;
+  int32_t* d_group_of = nullptr;
+  swarm::ResetGroup* d_groups = nullptr;
+  size_t groups_cap = 0;
+  int32_t* d_reset_envs = nullptr;
+  uint64_t reset_ordinal = 0;
 };
 
 // Device buffers of the engine: listed in e->allocs before anything else can
@@ -348,6 +362,35 @@ uint32_t angle_fixed(double dx, double dy) {
   const double phi = std::atan2(dy, dx);
   const int64_t a = (int64_t)std::nearbyint(phi / kTwoPi * kTwo32);
   return (uint32_t)(a & 0xFFFFFFFFLL);
+}
+
+// Host fp64 positions and directors [E][N][3] in the engine's own formats
+// (swarm_engine_upload_state, and the home state of a reset plan): q, img
+// [3][M], ang [M], in 3-D the normalised directors d3 [3][M].
+struct HostState {
+  std::vector<uint32_t> q, ang;
+  std::vector<int32_t> img;
+  std::vector<float> d3;
+};
+
+void state_to_fixed(const swarm_engine* e, const double* pos, const double* director,
+                    HostState* h) {
+  const size_t M = (size_t)e->st.m;
+  const int D = e->params.n_dims;
+  h->q.assign(3 * M, 0u);
+  h->img.assign(3 * M, 0);
+  h->ang.assign(M, 0u);
+  h->d3.assign(D == 3 ? 3 * M : 0, 0.0f);
+  for (size_t g = 0; g < M; ++g) {
+    for (int a = 0; a < D; ++a)
+      to_fixed(pos[3 * g + a], e->params.box[a], &h->q[a * M + g], &h->img[a * M + g]);
+    h->ang[g] = angle_fixed(director[3 * g + 0], director[3 * g + 1]);
+    if (D == 3) {
+      const double* v = director + 3 * g;
+      const double nm = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      for (int a = 0; a < 3; ++a) h->d3[a * M + g] = (float)(nm > 0.0 ? v[a] / nm : (a == 2));
+    }
+  }
 }
 
 }  // namespace
@@ -517,25 +560,13 @@ int swarm_engine_download_raw(swarm_engine_t* e, uint32_t* q, int32_t* img, uint
 int swarm_engine_upload_state(swarm_engine_t* e, const double* pos, const double* director) {
   if (!e || !pos || !director) return fail(SWARM_EINVAL, "null argument");
   if (const int frc = flush_check(e)) return frc;
-  const size_t M = (size_t)e->st.m;
-  std::vector<uint32_t> q(3 * M, 0u), ang(M);
-  std::vector<int32_t> img(3 * M, 0);
-  const int D = e->params.n_dims;
-  std::vector<float> d3(D == 3 ? 3 * M : 0);
-  for (size_t g = 0; g < M; ++g) {
-    for (int a = 0; a < D; ++a) to_fixed(pos[3 * g + a], e->params.box[a], &q[a * M + g], &img[a * M + g]);
-    ang[g] = angle_fixed(director[3 * g + 0], director[3 * g + 1]);
-    if (D == 3) {
-      const double* v = director + 3 * g;
-      const double nm = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-      for (int a = 0; a < 3; ++a) d3[a * M + g] = (float)(nm > 0.0 ? v[a] / nm : (a == 2));
-    }
-  }
-  if (D == 3) {
-    const int rc = swarm_engine_upload_directors(e, d3.data());
+  HostState h;
+  state_to_fixed(e, pos, director, &h);
+  if (e->params.n_dims == 3) {
+    const int rc = swarm_engine_upload_directors(e, h.d3.data());
     if (rc) return rc;
   }
-  const int rc = swarm_engine_upload_raw(e, q.data(), img.data(), ang.data());
+  const int rc = swarm_engine_upload_raw(e, h.q.data(), h.img.data(), h.ang.data());
   if (rc || !e->has_rod) return rc;
   // a rod's beads follow from its centre (the raw upload keeps them as given)
   if (const int src = launch_rod_snap(e)) return src;
@@ -658,6 +689,131 @@ int swarm_engine_remove_overlap(swarm_engine_t* e, int32_t n_steps, double gamma
   if (n_steps <= 0) return SWARM_OK;
   e->stepped = true;
   return launch_global(e, n_steps, 1, (float)gamma, (float)max_disp);
+}
+
+int swarm_engine_set_reset_plan(swarm_engine_t* e, const double* pos, const double* director,
+                                const swarm_reset_group_t* groups, int32_t n_groups) {
+  if (!e || !pos || !director || (n_groups > 0 && !groups))
+    return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (n_groups < 0) return fail(SWARM_EINVAL, "n_groups must be >= 0");
+  const int D = e->params.n_dims;
+  double half = e->params.box[0];
+  for (int a = 1; a < D; ++a) half = std::min(half, e->params.box[a]);
+  half *= 0.5;
+  std::vector<int32_t> group_of(e->n, -1);
+  std::vector<swarm::ResetGroup> dev(std::max(n_groups, 1));
+  for (int g = 0; g < n_groups; ++g) {
+    const swarm_reset_group_t& s = groups[g];
+    if (s.first < 0 || s.count < 0 || (int64_t)s.first + s.count > e->n)
+      return fail(SWARM_EINVAL, "reset group " + std::to_string(g) + " is out of range");
+    if (!std::isfinite(s.radius) || s.radius < 0.0)
+      return fail(SWARM_EINVAL, "reset group " + std::to_string(g) +
+                                    ": the radius must be finite and >= 0");
+    if (!(s.radius <= half))
+      return fail(SWARM_EINVAL, "reset group " + std::to_string(g) +
+                                    ": the radius exceeds half the shortest box edge");
+    swarm::ResetGroup& r = dev[g];
+    r = swarm::ResetGroup{};
+    for (int a = 0; a < D; ++a) {
+      if (!std::isfinite(s.centre[a]))
+        return fail(SWARM_EINVAL, "reset group " + std::to_string(g) + ": non-finite centre");
+      to_fixed(s.centre[a], e->params.box[a], &r.cq[a], &r.cimg[a]);
+    }
+    r.radius = (float)s.radius;
+    for (int i = s.first; i < s.first + s.count; ++i) {
+      if (group_of[i] != -1) return fail(SWARM_EINVAL, "reset groups overlap");
+      // (a group of radius 0 places nothing: its particles go home)
+      group_of[i] = s.radius > 0.0 ? g : -2;
+    }
+  }
+  for (int32_t& g : group_of) g = std::max(g, -1);
+  HostState h;
+  state_to_fixed(e, pos, director, &h);
+
+  const size_t M = (size_t)e->st.m;
+  if (!e->d_home_q) {
+    HIP_TRY(dev_malloc(e, &e->d_home_q, 3 * M * sizeof(uint32_t)));
+    HIP_TRY(dev_malloc(e, &e->d_home_img, 3 * M * sizeof(int32_t)));
+    HIP_TRY(dev_malloc(e, &e->d_home_ang, M * sizeof(uint32_t)));
+    if (D == 3) HIP_TRY(dev_malloc(e, &e->d_home_dir3, 3 * M * sizeof(float)));
+    HIP_TRY(dev_malloc(e, &e->d_group_of, (size_t)e->n * sizeof(int32_t)));
+    HIP_TRY(dev_malloc(e, &e->d_reset_envs, (size_t)e->n_envs * sizeof(int32_t)));
+  }
+  if (dev.size() > e->groups_cap) {
+    e->has_reset_plan = false;
+    e->groups_cap = 0;
+    HIP_TRY(dev_free(e, &e->d_groups));
+    HIP_TRY(dev_malloc(e, &e->d_groups, dev.size() * sizeof(swarm::ResetGroup)));
+    e->groups_cap = dev.size();
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_home_q, h.q.data(), 3 * M * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_home_img, h.img.data(), 3 * M * sizeof(int32_t),
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_home_ang, h.ang.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         e->stream));
+  if (D == 3)
+    HIP_TRY(hipMemcpyAsync(e->d_home_dir3, h.d3.data(), 3 * M * sizeof(float),
+                           hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_group_of, group_of.data(), group_of.size() * sizeof(int32_t),
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_groups, dev.data(), dev.size() * sizeof(swarm::ResetGroup),
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->has_reset_plan = true;
+  return SWARM_OK;
+}
+
+int swarm_engine_download_reuse_slots(swarm_engine_t* e, float* f_prev, float* tz_prev,
+                                      uint32_t* ang_prev, float* dir3_prev, float* txy_prev) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  const size_t M = (size_t)e->st.m;
+  const bool three_d = e->params.n_dims == 3;
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+  };
+  HIP_TRY(get(f_prev, e->st.f_prev, 2 * M * sizeof(float)));
+  HIP_TRY(get(tz_prev, e->st.tz_prev, 2 * M * sizeof(float)));
+  HIP_TRY(get(ang_prev, e->st.ang_prev, 2 * M * sizeof(uint32_t)));
+  if (three_d) {
+    HIP_TRY(get(dir3_prev, e->st.dir3_prev, 6 * M * sizeof(float)));
+    HIP_TRY(get(txy_prev, e->st.txy_prev, 4 * M * sizeof(float)));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+int swarm_engine_reset_envs(swarm_engine_t* e, const uint8_t* env_mask, int32_t sd_steps,
+                            double gamma, double max_disp) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  // their per-env kernels take the workgroup's index as the env
+  if (e->has_rod || e->has_ell || e->has_lv)
+    return fail(SWARM_EINVAL,
+                "reset in place is not supported with a rod, ellipsoids or the Langevin "
+                "thermostat");
+  if (sd_steps < 0) return fail(SWARM_EINVAL, "sd_steps must be >= 0");
+  if (!e->has_reset_plan) return fail(SWARM_ESTATE, "no reset plan (swarm_engine_set_reset_plan)");
+  std::vector<int32_t> envs;
+  for (int32_t k = 0; k < e->n_envs; ++k)
+    if (!env_mask || env_mask[k]) envs.push_back(k);
+  if (envs.empty()) return SWARM_OK;
+  // the listed envs' positions change under a pending build and the vision grid
+  e->prebuilt = false;
+  e->ride_stage = 0;
+  e->prebuilt_noise_steps = 0;
+  e->vgrid_ready = false;
+  HIP_TRY(hipMemcpyAsync(e->d_reset_envs, envs.data(), envs.size() * sizeof(int32_t),
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // (envs is this call's)
+  const int n_listed = (int)envs.size();
+  if (const int rc = launch_place(e, n_listed)) return rc;
+  ++e->reset_ordinal;
+  if (sd_steps == 0) return SWARM_OK;
+  e->stepped = true;
+  return launch_global_envs(e, n_listed, sd_steps, (float)gamma, (float)max_disp);
 }
 
 int swarm_engine_integrate(swarm_engine_t* e, int32_t n_steps) {

@@ -110,6 +110,7 @@ void allow_engine_lds(int device) {
   // (last: every kernel above keeps its place in the code object)
   swarm_select::each_bools<1>([&](auto gb) { allow(&swarm::k_ellipsoid_run<gb>); });
   allow(&swarm::k_langevin_run);
+  allow(&swarm::k_global_envs);
   (void)hipGetLastError();
   done.push_back(device);
 }
@@ -157,6 +158,36 @@ int launch_global(swarm_engine* e, int n_steps, int sd_mode, float g, float md) 
   hipLaunchKernelGGL(swarm::k_global, dim3(e->n_envs), dim3(1024),
                      global_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream, e->d_derived, e->st, e->sc,
                      n_steps, e->d_step, e->d_arrive, pl.lxg, pl.lyg, sd_mode, g, md);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+// swarm_engine_reset_envs (swarm_reset.cuh): the placement of the n_listed
+// envs in e->d_reset_envs, and n_steps of their overlap removal (launch_global
+// in steepest-descent mode over the list; plain colloids only).
+int launch_place(swarm_engine* e, int n_listed) {
+  const long items = (long)n_listed * e->n;
+  const swarm::ResetArgs a{e->d_reset_envs, n_listed,      e->d_group_of,  e->d_groups,
+                           e->d_home_q,     e->d_home_img, e->d_home_ang,  e->d_home_dir3,
+                           e->reset_ordinal, e->sc.cand_ok};
+  hipLaunchKernelGGL(swarm::k_place_envs, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                     e->stream, e->d_derived, e->st, a);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+int launch_global_envs(swarm_engine* e, int n_listed, int n_steps, float g, float md) {
+  const swarm::EnginePlan& pl = e->plan;
+  if (e->params.n_dims == 3)
+    hipLaunchKernelGGL(swarm::k_global3_envs, dim3(n_listed), dim3(1024),
+                       (16 + (size_t)(1 << (pl.lxg + pl.lyg + pl.lzg)) + 1) * 4, e->stream,
+                       e->d_derived, e->st, e->sc, e->d_reset_envs, n_steps, e->d_step, pl.lxg,
+                       pl.lyg, pl.lzg, g, md);
+  else
+    hipLaunchKernelGGL(swarm::k_global_envs, dim3(n_listed), dim3(1024),
+                       global_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream,
+                       e->d_derived, e->st, e->sc, e->d_reset_envs, n_steps, e->d_step, pl.lxg,
+                       pl.lyg, g, md);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }

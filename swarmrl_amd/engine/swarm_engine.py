@@ -308,6 +308,10 @@ class SwarmEngine(Engine):
         self._potential = None
         # add_flowfield: {"u": fp64 (nx, ny, nz, 3), "h": fp64 (3,), "gamma": float}
         self._flow = None
+        # add_colloids: (first, count, centre, radius) per call, the placement
+        # groups of reset_envs; _reset_plan_set: the library holds the plan
+        self._reset_groups: typing.List[tuple] = []
+        self._reset_plan_set = False
         self._native: _NativeEngine = None
         self._host_cache = None
         self._view = None
@@ -569,6 +573,8 @@ class SwarmEngine(Engine):
             radius_colloid, type_colloid, gamma_translation, gamma_rotation, aspect_ratio,
             mass, rinertia,
         )
+        self._reset_groups.append(
+            (len(self._types_list), int(n_colloids), init_center.copy(), float(init_rad)))
         for _ in range(n_colloids):
             positions, directions = [], []
             for e in range(self.n_envs):
@@ -1119,6 +1125,78 @@ class SwarmEngine(Engine):
         self._native.bind_stream()
         self._native.call("swarm_engine_remove_overlap", 1000, 0.1, 0.1)
         self.system.time = time
+        self._host_cache = None
+
+    def _reset_plan(self):
+        """What reset_envs hands to swarm_engine_set_reset_plan: the registered
+        points as the home state (pos, director fp64 [E, N, 3]) and one
+        placement group (first, count, centre, radius) per add_colloids call."""
+        pos = np.ascontiguousarray(np.stack([np.stack(v) for v in self._pos]), dtype=float)
+        dirs = np.ascontiguousarray(np.stack([np.stack(v) for v in self._dir]), dtype=float)
+        return pos, dirs, list(self._reset_groups)
+
+    def _validate_reset(self):
+        """What reset_envs cannot do, decided on the host: the per-env kernels
+        of these engines take the workgroup's index as the env."""
+        if self._rod is not None:
+            raise NotImplementedError("reset_envs with a rod is not implemented")
+        if self._has_ellipsoids():
+            raise NotImplementedError("reset_envs with ellipsoids is not implemented")
+        if self.params.thermostat_type == "langevin":
+            raise NotImplementedError(
+                "reset_envs under the Langevin thermostat is not implemented")
+        if not self.integration_initialised:
+            raise RuntimeError("nothing to reset: reset_envs needs a first call to integrate()")
+
+    def reset_envs(self, envs=None, remove_overlap: bool = True, h5_group_tag: str = None):
+        """Put envs (indices; None: all) back to a fresh random start on the
+        device: every colloid of an add_colloids call is drawn anew in its
+        disc (ball) with a new director, a colloid of add_colloid_on_point
+        returns to its point; velocities and actions are cleared and, with
+        remove_overlap, the reference's overlap removal (1000 steps, gamma
+        0.1, at most 0.1 per step) runs on those envs alone.  The engine, its
+        buffers and captured graphs stay; the other envs are untouched.
+
+        The draws are the device's own (Philox, keyed by the seed, the env and
+        the number of resets so far), not those of the numpy generators that
+        placed the first start.  The slice / write schedule (step_idx,
+        slice_idx, write_idx), system.time and the device's step and noise
+        counters go on: a reset starts no new clock.
+
+        h5_group_tag: the trajectory written so far is flushed and later
+        writes go to this group (the episodic trainers' cycle index)."""
+        self._validate_reset()
+        if envs is None:
+            mask = None
+        else:
+            idx = np.atleast_1d(np.asarray(envs, dtype=np.int64))
+            if idx.size and (idx.min() < 0 or idx.max() >= self.n_envs):
+                raise ValueError(f"envs must lie in [0, {self.n_envs})")
+            mask = np.zeros(self.n_envs, np.uint8)
+            mask[idx] = 1
+        if h5_group_tag is not None:
+            self.flush_trajectory()
+            self.h5_group_tag = h5_group_tag
+            self._writer.switch_group(h5_group_tag)
+            self.h5_time_steps_written = 0
+        if self._prebuild_pending is not None:  # a build forked from the old positions
+            if self._prebuild_pending[0] != "ride":
+                torch.cuda.current_stream().wait_stream(self._prebuild_pending[0])
+            self._prebuild_pending = None
+        self._native.bind_stream()
+        if not self._reset_plan_set:
+            pos, dirs, groups = self._reset_plan()
+            arr = (_capi.SwarmResetGroup * max(1, len(groups)))()
+            for k, (first, count, centre, radius) in enumerate(groups):
+                arr[k].first, arr[k].count, arr[k].radius = first, count, radius
+                for a in range(3):
+                    arr[k].centre[a] = float(centre[a])
+            self._native.call("swarm_engine_set_reset_plan", pos.ctypes.data, dirs.ctypes.data,
+                              ctypes.cast(arr, ctypes.c_void_p), len(groups))
+            self._reset_plan_set = True
+        self._native.call("swarm_engine_reset_envs",
+                          None if mask is None else mask.ctypes.data,
+                          1000 if remove_overlap else 0, 0.1, 0.1)
         self._host_cache = None
 
     # --------------------------------------------------------- trajectory

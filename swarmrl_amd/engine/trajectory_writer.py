@@ -24,6 +24,13 @@ class _H5Writer:
 
         self._h5py = h5py
         self.path = path
+        self._n_colloids = n_colloids
+        self._chunk = chunk
+        self.switch_group(group)
+
+    def switch_group(self, group: str):
+        """Later writes go to `group` (created like the first), from offset 0."""
+        h5py, path, n_colloids, chunk = self._h5py, self.path, self._n_colloids, self._chunk
         self.group = group
         with h5py.File(path.as_posix(), "a") as f:
             g = f.require_group(group)
@@ -56,6 +63,10 @@ class _NpzWriter:
         self.group = group
         self._count = 0
 
+    def switch_group(self, group: str):
+        """Later chunks carry `group`; the chunk numbering goes on."""
+        self.group = group
+
     def write(self, values: dict, offset: int):
         out = self.path.with_name(f"{self.path.name}.chunk{self._count:06d}.npz")
         np.savez(out, group=np.array(self.group), offset=np.array(offset), **values)
@@ -70,6 +81,26 @@ def make_writer(path, group: str, n_colloids: int, chunk: int):
         return _H5Writer(path, group, n_colloids, chunk)
     except ImportError:
         return _NpzWriter(path, group, n_colloids, chunk)
+
+
+def read_groups(path) -> list:
+    """The groups of a trajectory file (either format), in the order written."""
+    path = pathlib.Path(path)
+    try:
+        import h5py
+
+        if path.exists():
+            with h5py.File(path.as_posix(), "r") as f:
+                return list(f.keys())
+    except ImportError:
+        pass
+    groups = []
+    for c in sorted(path.parent.glob(path.name + ".chunk*.npz")):
+        with np.load(c, allow_pickle=False) as z:
+            g = str(z["group"])
+        if g not in groups:
+            groups.append(g)
+    return groups
 
 
 def read_trajectory(path) -> dict:
