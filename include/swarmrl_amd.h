@@ -428,6 +428,31 @@ int swarm_engine_reset_envs(swarm_engine_t *e, const uint8_t *env_mask,
                             int32_t sd_steps, double gamma,
                             double max_displacement);
 
+/* swarm_engine_reset_envs for the envs a device mask marks (d_mask: device
+ * uint8 [E], non-zero: reset), without a host copy and without a
+ * synchronisation: every launch has a grid that does not depend on the mask's
+ * contents, so the call can be captured into a graph and replayed with other
+ * mask contents.  A marked env gets exactly what a listed env of
+ * swarm_engine_reset_envs gets (placement, zeroed velocities and actions,
+ * both reuse_forces slots, its candidate lists dropped, sd_steps of the
+ * overlap removal); only the draw counter differs: the ordinal is
+ * 2^63 | c_env, c_env the device-mask resets this env has had so far (a
+ * per-env device counter, bumped for marked envs only), so the k-th reset of
+ * an env is the same whatever the other envs do and the ordinals 0, 1, ... of
+ * swarm_engine_reset_envs are not disturbed.  An unmarked env is not touched
+ * by a single store; an all-zero mask changes nothing.  The host cannot know
+ * whether an env was marked: a pending check is flushed and a pending build
+ * discarded whatever the mask holds.  SWARM_ESTATE without a reset plan;
+ * SWARM_EINVAL on an engine with a rod, ellipsoids or the Langevin
+ * thermostat, for sd_steps < 0 and for a null mask. */
+int swarm_engine_reset_marked(swarm_engine_t *e, const uint8_t *d_mask,
+                              int32_t sd_steps, double gamma,
+                              double max_displacement);
+
+/* counts (host uint32 [E]): per env, the resets swarm_engine_reset_marked has
+ * given it (0 before a reset plan is set).  Synchronous. */
+int swarm_engine_reset_counts(swarm_engine_t *e, uint32_t *counts);
+
 /* n_steps Brownian-dynamics sub-steps with WCA pair forces; replaces
  * system.integrator.run(k, reuse_forces=True, recalc_forces=False)
  * (espresso.py:1304-1306).  Asynchronous on the engine stream. */
@@ -671,6 +696,15 @@ int swarm_field_transform(swarm_engine_t *e, const int32_t *agent_idx,
                           int32_t *hist_img, float decay_a, float decay_b,
                           float scale, int32_t clip_at_zero, float *out);
 
+/* The history of swarm_field_distance / swarm_field_transform after a
+ * swarm_engine_reset_marked: for every agent of an env with d_mask[env] != 0
+ * (device uint8 [E]) history <- current position, what init_only does for
+ * every env; the history of an unmarked env is not stored to.  No host copy,
+ * no synchronisation, a grid that does not depend on the mask: capturable. */
+int swarm_field_history_marked(swarm_engine_t *e, const uint8_t *d_mask,
+                               const int32_t *agent_idx, int32_t n_agents,
+                               uint32_t *hist_q, int32_t *hist_img);
+
 /* Parity helper: all pairs (i<j) of env `env` closer than `cutoff`
  * (minimum image if periodic) as int32 [max_pairs][2] (host), count in
  * *n_pairs; returns SWARM_ECAPACITY if more than max_pairs. */
@@ -853,6 +887,40 @@ int swarm_ppo_epoch_step(const float *x, int32_t T, int32_t S, int32_t d_in,
                          int32_t hidden, int32_t k, float gamma, float lambda, float clip_eps,
                          float entropy_coef, const swarm_adam_t *adam, void *workspace,
                          int64_t workspace_bytes, float *grad, void *stream);
+
+/* swarm_ppo_epoch_grad, swarm_ppo_epoch_step and swarm_ppo_deep_epoch_grad
+ * for a trajectory in which envs ended episodes on their own
+ * (swarm_engine_reset_marked): the same calls plus dones (device uint8
+ * [T][S / per_env], non-zero: the env was reset after step t) and per_env,
+ * column col of the T x S grid belonging to env col / per_env.  Where
+ * dones[t][env] is set the advantage estimate treats step t as the last step
+ * is treated -- delta_t = r_t - V_t, nothing carried in from t + 1 -- and in
+ * the backward pass later values do not reach earlier returns.  The
+ * normalisation of the advantages runs over all T x S samples.  With all-zero
+ * dones the gradient is bit-identical to the call without.  SWARM_EINVAL for
+ * null dones and for a per_env below 1 or not dividing S; otherwise the
+ * limits, workspaces and determinism of the calls they extend. */
+int swarm_ppo_epoch_grad_ep(const float *x, int32_t T, int32_t S, int32_t d_in,
+                            const int64_t *actions, const float *old_logp, const float *rewards,
+                            const float *w1, const float *b1, int32_t hidden, const float *wa,
+                            const float *ba, int32_t k, const float *wc, const float *bc,
+                            float gamma, float lambda, float clip_eps, float entropy_coef,
+                            void *workspace, int64_t workspace_bytes, float *grad, void *stream,
+                            const uint8_t *dones, int32_t per_env);
+int swarm_ppo_epoch_step_ep(const float *x, int32_t T, int32_t S, int32_t d_in,
+                            const int64_t *actions, const float *old_logp, const float *rewards,
+                            int32_t hidden, int32_t k, float gamma, float lambda, float clip_eps,
+                            float entropy_coef, const swarm_adam_t *adam, void *workspace,
+                            int64_t workspace_bytes, float *grad, void *stream,
+                            const uint8_t *dones, int32_t per_env);
+int swarm_ppo_deep_epoch_grad_ep(const float *x, int32_t T, int32_t S, int32_t d_in,
+                                 const int64_t *actions, const float *old_logp,
+                                 const float *rewards, int32_t n_hidden, const int32_t *widths,
+                                 const float *const *w, const float *const *b, const float *wa,
+                                 const float *ba, int32_t k, const float *wc, const float *bc,
+                                 float gamma, float lambda, float clip_eps, float entropy_coef,
+                                 void *workspace, int64_t workspace_bytes, float *grad,
+                                 void *stream, const uint8_t *dones, int32_t per_env);
 
 /* The rollout policy of an ensemble of n_members independent actor-critic
  * MLPs in one launch.  Replaces the per-member policy calls of the

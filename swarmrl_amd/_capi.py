@@ -174,6 +174,11 @@ _SIGNATURES = {
         ctypes.c_int,
         [_P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_double],
     ),
+    "swarm_engine_reset_marked": (
+        ctypes.c_int,
+        [_P, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_double],
+    ),
+    "swarm_engine_reset_counts": (ctypes.c_int, [_P, _P]),
     "swarm_engine_integrate": (ctypes.c_int, [_P, ctypes.c_int32]),
     "swarm_engine_prebuild": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
     "swarm_engine_prebuild_noise": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
@@ -237,6 +242,24 @@ _SIGNATURES = {
         [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
          ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
          ctypes.POINTER(SwarmAdam), _P, ctypes.c_int64, _P, _P],
+    ),
+    "swarm_ppo_epoch_grad_ep": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32,
+         _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+         ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32],
+    ),
+    "swarm_ppo_epoch_step_ep": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+         ctypes.POINTER(SwarmAdam), _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32],
+    ),
+    "swarm_ppo_deep_epoch_grad_ep": (
+        ctypes.c_int,
+        [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int32, _P, _P,
+         _P, _P, _P, ctypes.c_int32, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+         ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32],
     ),
     "swarm_policy_ensemble_sample": (
         ctypes.c_int,
@@ -324,6 +347,7 @@ _SIGNATURES = {
         [_P, _P, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float,
          ctypes.c_float, ctypes.c_int32, _P],
     ),
+    "swarm_field_history_marked": (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, _P, _P]),
     "swarm_engine_set_torque_xy": (ctypes.c_int, [_P, _P, ctypes.c_int32]),
     "swarm_engine_upload_directors": (ctypes.c_int, [_P, _P]),
     "swarm_engine_download_directors": (ctypes.c_int, [_P, _P]),

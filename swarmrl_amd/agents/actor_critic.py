@@ -91,6 +91,18 @@ class ActorCriticAgent(Agent):
         self.observable.initialize(colloids)
         self.task.initialize(colloids)
 
+    def reinitialize_envs(self, view, mask):
+        """After an auto-reset: the marked envs' histories from their fresh
+        start (observable and task)."""
+        self.observable.reinitialize_envs(view, mask)
+        self.task.reinitialize_envs(view, mask)
+
+    def record_dones(self, mask):
+        """dones[t][e] = 1: env e was reset after transition t (one entry per
+        reward).  A copy is kept: the caller may reuse the mask's buffer."""
+        if self.train:
+            self.trajectory.dones.append(mask.clone())
+
     def reset_trajectory(self):
         self.task.kill_switch = False
         self.trajectory = TrajectoryInformation(particle_type=self.particle_type)

@@ -24,3 +24,13 @@ class Agent:
 
     def calc_reward(self, colloids, external_reward: float = 0.0) -> None:
         raise NotImplementedError("Implemented in Child class.")
+
+    def record_dones(self, mask) -> None:
+        """The envs an auto-reset engine resets after the last transition
+        (uint8 [E] device tensor); agents that do not train ignore it."""
+        pass
+
+    def reinitialize_envs(self, view, mask) -> None:
+        """Re-initialise per-env histories after the reset of the marked
+        envs; agents without histories ignore it."""
+        pass

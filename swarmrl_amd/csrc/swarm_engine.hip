@@ -244,6 +244,8 @@ struct swarm_engine {
   size_t groups_cap = 0;
   int32_t* d_reset_envs = nullptr;
   uint64_t reset_ordinal = 0;
+  // swarm_engine_reset_marked: per env, the device-mask resets it has had
+  uint32_t* d_reset_counts = nullptr;
 };
 
 // Device buffers of the engine: listed in e->allocs before anything else can
@@ -739,6 +741,9 @@ int swarm_engine_set_reset_plan(swarm_engine_t* e, const double* pos, const doub
     if (D == 3) HIP_TRY(dev_malloc(e, &e->d_home_dir3, 3 * M * sizeof(float)));
     HIP_TRY(dev_malloc(e, &e->d_group_of, (size_t)e->n * sizeof(int32_t)));
     HIP_TRY(dev_malloc(e, &e->d_reset_envs, (size_t)e->n_envs * sizeof(int32_t)));
+    HIP_TRY(dev_malloc(e, &e->d_reset_counts, (size_t)e->n_envs * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(e->d_reset_counts, 0, (size_t)e->n_envs * sizeof(uint32_t),
+                           e->stream));
   }
   if (dev.size() > e->groups_cap) {
     e->has_reset_plan = false;
@@ -814,6 +819,55 @@ int swarm_engine_reset_envs(swarm_engine_t* e, const uint8_t* env_mask, int32_t 
   if (sd_steps == 0) return SWARM_OK;
   e->stepped = true;
   return launch_global_envs(e, n_listed, sd_steps, (float)gamma, (float)max_disp);
+}
+
+int swarm_engine_reset_marked(swarm_engine_t* e, const uint8_t* d_mask, int32_t sd_steps,
+                              double gamma, double max_disp) {
+  if (!e) return fail(SWARM_EINVAL, "null engine");
+  if (const int frc = flush_check(e)) return frc;
+  if (e->has_rod || e->has_ell || e->has_lv)
+    return fail(SWARM_EINVAL,
+                "reset in place is not supported with a rod, ellipsoids or the Langevin "
+                "thermostat");
+  if (sd_steps < 0) return fail(SWARM_EINVAL, "sd_steps must be >= 0");
+  if (!d_mask) return fail(SWARM_EINVAL, "null mask");
+  if (!e->has_reset_plan) return fail(SWARM_ESTATE, "no reset plan (swarm_engine_set_reset_plan)");
+  // the host cannot know whether an env is marked: as if one were
+  e->prebuilt = false;
+  e->ride_stage = 0;
+  e->prebuilt_noise_steps = 0;
+  e->vgrid_ready = false;
+  if (const int rc = launch_place_marked(e, d_mask)) return rc;
+  if (sd_steps == 0) return SWARM_OK;
+  e->stepped = true;
+  return launch_global_marked(e, d_mask, sd_steps, (float)gamma, (float)max_disp);
+}
+
+int swarm_engine_reset_counts(swarm_engine_t* e, uint32_t* counts) {
+  if (!e || !counts) return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (!e->d_reset_counts) {  // (no plan yet: no marked reset can have run)
+    std::memset(counts, 0, (size_t)e->n_envs * sizeof(uint32_t));
+    return SWARM_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(counts, e->d_reset_counts, (size_t)e->n_envs * sizeof(uint32_t),
+                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return SWARM_OK;
+}
+
+int swarm_field_history_marked(swarm_engine_t* e, const uint8_t* d_mask, const int32_t* agent_idx,
+                               int32_t n_agents, uint32_t* hist_q, int32_t* hist_img) {
+  if (!e || !d_mask || !agent_idx || !hist_q || !hist_img)
+    return fail(SWARM_EINVAL, "null argument");
+  if (const int frc = flush_check(e)) return frc;
+  if (n_agents <= 0) return SWARM_OK;
+  const long items = (long)n_agents * e->n_envs;
+  hipLaunchKernelGGL(swarm::k_field_history_marked, dim3((unsigned)((items + 255) / 256)),
+                     dim3(256), 0, e->stream, e->st, d_mask, agent_idx, n_agents, e->n_envs,
+                     hist_q, hist_img);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
 }
 
 int swarm_engine_integrate(swarm_engine_t* e, int32_t n_steps) {

@@ -111,6 +111,7 @@ void allow_engine_lds(int device) {
   swarm_select::each_bools<1>([&](auto gb) { allow(&swarm::k_ellipsoid_run<gb>); });
   allow(&swarm::k_langevin_run);
   allow(&swarm::k_global_envs);
+  allow(&swarm::k_global_marked);
   (void)hipGetLastError();
   done.push_back(device);
 }
@@ -188,6 +189,39 @@ int launch_global_envs(swarm_engine* e, int n_listed, int n_steps, float g, floa
                        global_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream,
                        e->d_derived, e->st, e->sc, e->d_reset_envs, n_steps, e->d_step, pl.lxg,
                        pl.lyg, g, md);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+// swarm_engine_reset_marked: the same over every env, the marked ones acting;
+// the grids do not depend on the mask.  The per-env reset counts are bumped
+// in a launch of their own after the placement has read them.
+int launch_place_marked(swarm_engine* e, const uint8_t* d_mask) {
+  const long items = (long)e->n_envs * e->n;
+  const swarm::ResetArgs a{nullptr,     e->n_envs,     e->d_group_of, e->d_groups,
+                           e->d_home_q, e->d_home_img, e->d_home_ang, e->d_home_dir3,
+                           0,           e->sc.cand_ok};
+  hipLaunchKernelGGL(swarm::k_place_marked, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                     e->stream, e->d_derived, e->st, a, d_mask, e->d_reset_counts);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(swarm::k_count_marked, dim3((unsigned)((e->n_envs + 255) / 256)), dim3(256),
+                     0, e->stream, d_mask, e->d_reset_counts, e->n_envs);
+  HIP_TRY(hipGetLastError());
+  return SWARM_OK;
+}
+
+int launch_global_marked(swarm_engine* e, const uint8_t* d_mask, int n_steps, float g, float md) {
+  const swarm::EnginePlan& pl = e->plan;
+  if (e->params.n_dims == 3)
+    hipLaunchKernelGGL(swarm::k_global3_marked, dim3(e->n_envs), dim3(1024),
+                       (16 + (size_t)(1 << (pl.lxg + pl.lyg + pl.lzg)) + 1) * 4, e->stream,
+                       e->d_derived, e->st, e->sc, d_mask, n_steps, e->d_step, pl.lxg, pl.lyg,
+                       pl.lzg, g, md);
+  else
+    hipLaunchKernelGGL(swarm::k_global_marked, dim3(e->n_envs), dim3(1024),
+                       global_lds_bytes(pl.lxg, pl.lyg, e->n, e->params.n_dims), e->stream,
+                       e->d_derived, e->st, e->sc, d_mask, n_steps, e->d_step, pl.lxg, pl.lyg, g,
+                       md);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }

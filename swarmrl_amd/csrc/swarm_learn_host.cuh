@@ -274,18 +274,34 @@ struct PpoProfile {
 };
 thread_local PpoProfile g_ppo_prof;
 
+// k_ppo_gae_ep of a shape's variant (defined after every other launch of this
+// file: its instantiations come last in the code object).
+int launch_gae_ep(int hidden, int d_in, int k, dim3 grid, hipStream_t s, const float* rewards,
+                  const float* values, int T, int S, float gamma, float lambda, float* adv,
+                  float* dv, double* spart, int gae_blocks, const swarm::PpoPack& pk,
+                  const uint8_t* dones, int per_env);
+
+// dones [T][S / per_env] of the *_ep entries: whole envs only.
+const char* dones_limits(int32_t S, int32_t per_env) {
+  if (per_env < 1 || S % per_env != 0) return "per_env must be >= 1 and divide S";
+  return nullptr;
+}
+
 // V of every sample, GAE + dL/dV (+ the table), the gradients, their reduce
-// (with adam: the optimizer step fused into it).
+// (with adam: the optimizer step fused into it).  dones non-null: the GAE
+// across episode ends (k_ppo_gae_ep).
 int ppo_epoch(const float* x, int32_t T, int32_t S, int32_t d_in, const int64_t* actions,
               const float* old_logp, const float* rewards, const float* w1, const float* b1,
               int32_t hidden, const float* wa, const float* ba, int32_t k, const float* wc,
               const float* bc, float gamma, float lambda, float clip_eps, float entropy_coef,
               void* workspace, int64_t workspace_bytes, float* grad, void* stream,
-              const swarm_adam_t* adam) {
+              const swarm_adam_t* adam, const uint8_t* dones = nullptr, int32_t per_env = 1) {
   if (!x || !actions || !old_logp || !rewards || !w1 || !b1 || !wa || !ba || !wc || !bc ||
       !workspace || !grad)
     return fail(SWARM_EINVAL, "null argument");
   if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
+  if (dones)
+    if (const char* why = dones_limits(S, per_env)) return fail(SWARM_EINVAL, why);
   if ((long)T * S > INT32_MAX) return fail(SWARM_ECAPACITY, "T x S < 2^31 samples");
   if (const char* why = ppo_limits(d_in, hidden, k)) return fail(SWARM_ECAPACITY, why);
   const int n = T * S;
@@ -313,7 +329,11 @@ int ppo_epoch(const float* x, int32_t T, int32_t S, int32_t d_in, const int64_t*
                          dim3(256), 0, s, x, n, d_in, w1, b1, hidden, wc, bc, values);
     const swarm::PpoPack pk{w1, b1, wa, wc, d_in, hidden, k, pl.table_rows, table};
     const dim3 ggrid((unsigned)(gae_blocks + (pl.table_floats + 255) / 256));
-    if (T <= 32)
+    if (dones) {
+      if (const int grc = launch_gae_ep(hidden, d_in, k, ggrid, s, rewards, values, T, S, gamma,
+                                        lambda, adv, dv, spart, gae_blocks, pk, dones, per_env))
+        return grc;
+    } else if (T <= 32)
       hipLaunchKernelGGL((swarm::k_ppo_gae<32, DD, KK>), ggrid, dim3(256), 0, s, rewards, values,
                          T, S, gamma, lambda, adv, dv, spart, gae_blocks, pk);
     else
@@ -629,20 +649,24 @@ int64_t swarm_ppo_deep_workspace_bytes(int32_t T, int32_t S, int32_t d_in, int32
                                      deep_ppo_grad_size(d_in, n_hidden, widths, k)).total;
 }
 
-int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
-                              const int64_t* actions, const float* old_logp,
-                              const float* rewards, int32_t n_hidden, const int32_t* widths,
-                              const float* const* w, const float* const* b, const float* wa,
-                              const float* ba, int32_t k, const float* wc, const float* bc,
-                              float gamma, float lambda, float clip_eps, float entropy_coef,
-                              void* workspace, int64_t workspace_bytes, float* grad,
-                              void* stream) {
+namespace {
+
+// swarm_ppo_deep_epoch_grad, and with dones its _ep sibling.
+int deep_ppo_epoch(const float* x, int32_t T, int32_t S, int32_t d_in, const int64_t* actions,
+                   const float* old_logp, const float* rewards, int32_t n_hidden,
+                   const int32_t* widths, const float* const* w, const float* const* b,
+                   const float* wa, const float* ba, int32_t k, const float* wc, const float* bc,
+                   float gamma, float lambda, float clip_eps, float entropy_coef, void* workspace,
+                   int64_t workspace_bytes, float* grad, void* stream, const uint8_t* dones,
+                   int32_t per_env) {
   if (!x || !actions || !old_logp || !rewards || !widths || !w || !b || !wa || !ba || !wc ||
       !bc || !workspace || !grad)
     return fail(SWARM_EINVAL, "null argument");
   if (T < 1 || S < 1) return fail(SWARM_EINVAL, "T, S >= 1");
   if ((long)T * S > INT32_MAX) return fail(SWARM_ECAPACITY, "T x S < 2^31 samples");
   if (const char* why = deep_limits(d_in, n_hidden, widths, k)) return fail(SWARM_ECAPACITY, why);
+  if (dones)
+    if (const char* why = dones_limits(S, per_env)) return fail(SWARM_EINVAL, why);
   swarm::DeepPpoArgs p{};
   if (!deep_fill(d_in, n_hidden, widths, w, b, wa, ba, k, p, nullptr))
     return fail(SWARM_EINVAL, "null parameter");
@@ -664,7 +688,12 @@ int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in
                      wc, bc, values);
   // k_ppo_gae as it stands, without pack workgroups (n_gae = its grid)
   const swarm::PpoPack none{};
-  if (T <= 32)
+  if (dones) {
+    if (const int grc = launch_gae_ep(1, 1, 4, dim3((unsigned)gae_blocks), s, rewards, values, T,
+                                      S, gamma, lambda, adv, dv, spart, gae_blocks, none, dones,
+                                      per_env))
+      return grc;
+  } else if (T <= 32)
     hipLaunchKernelGGL((swarm::k_ppo_gae<32, 1, 4>), dim3((unsigned)gae_blocks), dim3(256), 0, s,
                        rewards, values, T, S, gamma, lambda, adv, dv, spart, gae_blocks, none);
   else
@@ -686,6 +715,63 @@ int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in
                      p.partial, blocks, p.size, grad);
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
+}
+
+}  // namespace
+
+int swarm_ppo_deep_epoch_grad(const float* x, int32_t T, int32_t S, int32_t d_in,
+                              const int64_t* actions, const float* old_logp,
+                              const float* rewards, int32_t n_hidden, const int32_t* widths,
+                              const float* const* w, const float* const* b, const float* wa,
+                              const float* ba, int32_t k, const float* wc, const float* bc,
+                              float gamma, float lambda, float clip_eps, float entropy_coef,
+                              void* workspace, int64_t workspace_bytes, float* grad,
+                              void* stream) {
+  return deep_ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, n_hidden, widths, w, b, wa, ba,
+                        k, wc, bc, gamma, lambda, clip_eps, entropy_coef, workspace,
+                        workspace_bytes, grad, stream, nullptr, 1);
+}
+
+int swarm_ppo_epoch_grad_ep(const float* x, int32_t T, int32_t S, int32_t d_in,
+                            const int64_t* actions, const float* old_logp, const float* rewards,
+                            const float* w1, const float* b1, int32_t hidden, const float* wa,
+                            const float* ba, int32_t k, const float* wc, const float* bc,
+                            float gamma, float lambda, float clip_eps, float entropy_coef,
+                            void* workspace, int64_t workspace_bytes, float* grad, void* stream,
+                            const uint8_t* dones, int32_t per_env) {
+  if (!dones) return fail(SWARM_EINVAL, "null argument");
+  return ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, w1, b1, hidden, wa, ba, k, wc, bc,
+                   gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
+                   nullptr, dones, per_env);
+}
+
+int swarm_ppo_epoch_step_ep(const float* x, int32_t T, int32_t S, int32_t d_in,
+                            const int64_t* actions, const float* old_logp, const float* rewards,
+                            int32_t hidden, int32_t k, float gamma, float lambda, float clip_eps,
+                            float entropy_coef, const swarm_adam_t* adam, void* workspace,
+                            int64_t workspace_bytes, float* grad, void* stream,
+                            const uint8_t* dones, int32_t per_env) {
+  if (!adam || !dones) return fail(SWARM_EINVAL, "null argument");
+  if (!(adam->beta1 >= 0.0f && adam->beta1 < 1.0f && adam->beta2 >= 0.0f && adam->beta2 < 1.0f))
+    return fail(SWARM_EINVAL, "Adam betas must be in [0, 1)");
+  return ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, adam->param[0], adam->param[1],
+                   hidden, adam->param[2], adam->param[3], k, adam->param[4], adam->param[5],
+                   gamma, lambda, clip_eps, entropy_coef, workspace, workspace_bytes, grad, stream,
+                   adam, dones, per_env);
+}
+
+int swarm_ppo_deep_epoch_grad_ep(const float* x, int32_t T, int32_t S, int32_t d_in,
+                                 const int64_t* actions, const float* old_logp,
+                                 const float* rewards, int32_t n_hidden, const int32_t* widths,
+                                 const float* const* w, const float* const* b, const float* wa,
+                                 const float* ba, int32_t k, const float* wc, const float* bc,
+                                 float gamma, float lambda, float clip_eps, float entropy_coef,
+                                 void* workspace, int64_t workspace_bytes, float* grad,
+                                 void* stream, const uint8_t* dones, int32_t per_env) {
+  if (!dones) return fail(SWARM_EINVAL, "null argument");
+  return deep_ppo_epoch(x, T, S, d_in, actions, old_logp, rewards, n_hidden, widths, w, b, wa, ba,
+                        k, wc, bc, gamma, lambda, clip_eps, entropy_coef, workspace,
+                        workspace_bytes, grad, stream, dones, per_env);
 }
 
 // ---- entry points: ensembles, M independent actor-critic MLPs per launch
@@ -951,3 +1037,26 @@ int swarm_ppo_deep_ensemble_epoch_grad(const float* x, int32_t n_members, int32_
   HIP_TRY(hipGetLastError());
   return SWARM_OK;
 }
+
+// ---- the GAE across episode ends (declared above ppo_epoch)
+
+namespace {
+
+int launch_gae_ep(int hidden, int d_in, int k, dim3 grid, hipStream_t s, const float* rewards,
+                  const float* values, int T, int S, float gamma, float lambda, float* adv,
+                  float* dv, double* spart, int gae_blocks, const swarm::PpoPack& pk,
+                  const uint8_t* dones, int per_env) {
+  return ppo_variant(hidden, d_in, k, [&](auto, auto DD_, auto KK_) -> int {
+    constexpr int DD = DD_, KK = KK_;
+    if (T <= 32)
+      hipLaunchKernelGGL((swarm::k_ppo_gae_ep<32, DD, KK>), grid, dim3(256), 0, s, rewards, values,
+                         T, S, gamma, lambda, adv, dv, spart, gae_blocks, pk, dones, per_env);
+    else
+      hipLaunchKernelGGL((swarm::k_ppo_gae_ep<0, DD, KK>), grid, dim3(256), 0, s, rewards, values,
+                         T, S, gamma, lambda, adv, dv, spart, gae_blocks, pk, dones, per_env);
+    HIP_TRY(hipGetLastError());
+    return SWARM_OK;
+  });
+}
+
+}  // namespace

@@ -205,18 +205,24 @@ __global__ __launch_bounds__(256) void k_ppo_values_split(const float* __restric
 // arithmetic is the same in either form.
 // Workgroups past n_gae (blockIdx.x >= n_gae) lay out the gradient
 // kernel's parameter table instead (PpoPack: no launch of their own).
+// kDones (k_ppo_gae_ep): dones [T][S / per_env] marks the steps after which a
+// column's env (col / per_env) was reset; such a step is treated as the last
+// one is -- delta_t = r_t - V_t, nothing carried in from t + 1 -- and the
+// backward carry is zeroed after it: later values do not reach earlier returns.
 struct PpoPack {
   const float *w1, *b1, *wa, *wc;
   int d, hidden, k, rows;
   float* table;
 };
 
-template <int TM, int D, int K>
+template <int TM, int D, int K, bool kDones = false>
 __device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
                                              const float* __restrict__ values, int T, int S,
                                              float gamma, float lambda, float* __restrict__ adv,
                                              float* __restrict__ dv, double* __restrict__ part,
-                                             int n_gae, const PpoPack& pk) {
+                                             int n_gae, const PpoPack& pk,
+                                             const uint8_t* __restrict__ dones = nullptr,
+                                             int per_env = 1) {
   __shared__ double red[2][4];
   if ((int)blockIdx.x >= n_gae) {
     ppo_pack_entry<D, K>(pk.w1, pk.b1, pk.d, pk.hidden, pk.wa, pk.k, pk.wc, pk.rows,
@@ -228,17 +234,23 @@ __device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
   const float gl = gamma * lambda, g1 = gamma * (1.0f - lambda);
   if (col < S && TM > 0) {
     float vr[TM > 0 ? TM : 1], rr[TM > 0 ? TM : 1];
+    uint32_t ends = 0u;  // kDones: bit t, the column's env was reset after step t
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       vr[t] = t < T ? values[(size_t)t * S + col] : 0.0f;
       rr[t] = t < T ? rewards[(size_t)t * S + col] : 0.0f;
+      if constexpr (kDones)
+        if (t < T && dones[(size_t)t * (S / per_env) + col / per_env]) ends |= 1u << t;
     }
     float gae = 0.0f;
 #pragma unroll
     for (int t = TM - 1; t >= 0; --t) {
       if (t < T) {
         const float v = vr[t];
-        const float delta = t != T - 1 ? rr[t] + gamma * vr[t < TM - 1 ? t + 1 : t] - v : rr[t] - v;
+        const bool end = kDones && ((ends >> t) & 1u);
+        const float delta =
+            t != T - 1 && !end ? rr[t] + gamma * vr[t < TM - 1 ? t + 1 : t] - v : rr[t] - v;
+        if (end) gae = 0.0f;
         gae = delta + gl * gae;
         adv[(size_t)t * S + col] = gae;
         rr[t] = 0.5f * fminf(fmaxf(v - (gae + v), -1.0f), 1.0f);  // direct dL/dV
@@ -253,6 +265,7 @@ __device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
         const float g = rr[t];
         dv[(size_t)t * S + col] = g - g1 * carry;
         carry = gl * carry + g;
+        if (kDones && ((ends >> t) & 1u)) carry = 0.0f;
       }
     }
   } else if (col < S) {
@@ -260,7 +273,11 @@ __device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
     for (int t = T - 1; t >= 0; --t) {
       const size_t i = (size_t)t * S + col;
       const float v = values[i];
-      const float delta = t != T - 1 ? rewards[i] + gamma * values[i + S] - v : rewards[i] - v;
+      bool end = false;
+      if constexpr (kDones) end = dones[(size_t)t * (S / per_env) + col / per_env] != 0;
+      const float delta =
+          t != T - 1 && !end ? rewards[i] + gamma * values[i + S] - v : rewards[i] - v;
+      if (end) gae = 0.0f;
       gae = delta + gl * gae;
       adv[i] = gae;
       // critic term 0.5 huber(V, R), R = A + V: d/dV (direct) = 0.5 clip(V - R, -1, 1)
@@ -275,6 +292,8 @@ __device__ __forceinline__ void ppo_gae_body(const float* __restrict__ rewards,
       const float g = dv[i];
       dv[i] = g - g1 * carry;
       carry = gl * carry + g;
+      if constexpr (kDones)
+        if (dones[(size_t)t * (S / per_env) + col / per_env]) carry = 0.0f;
     }
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -306,6 +325,21 @@ __global__ __launch_bounds__(256) void k_ppo_gae(const float* __restrict__ rewar
                                                  double* __restrict__ part, int n_gae,
                                                  PpoPack pk) {
   ppo_gae_body<TM, D, K>(rewards, values, T, S, gamma, lambda, adv, dv, part, n_gae, pk);
+}
+
+// k_ppo_gae across episode ends (swarm_ppo_epoch_grad_ep and its siblings):
+// dones device uint8 [T][S / per_env], column col belongs to env col / per_env.
+template <int TM, int D, int K>
+__global__ __launch_bounds__(256) void k_ppo_gae_ep(const float* __restrict__ rewards,
+                                                    const float* __restrict__ values, int T, int S,
+                                                    float gamma, float lambda,
+                                                    float* __restrict__ adv,
+                                                    float* __restrict__ dv,
+                                                    double* __restrict__ part, int n_gae,
+                                                    PpoPack pk, const uint8_t* __restrict__ dones,
+                                                    int per_env) {
+  ppo_gae_body<TM, D, K, true>(rewards, values, T, S, gamma, lambda, adv, dv, part, n_gae, pk,
+                               dones, per_env);
 }
 
 // The sums of the GAE blocks' partials, in a fixed order (thread-strided

@@ -10,6 +10,10 @@
 //   k_global_envs    k_global in steepest-descent mode, env = envs[blockIdx.x]
 //   k_global3_envs   k_global3 likewise
 //
+//   k_place_marked, k_count_marked, k_global_marked, k_global3_marked,
+//   k_field_history_marked    the same for the envs a device mask marks
+//                    (swarm_engine_reset_marked, swarm_field_history_marked)
+//
 // An env that is not listed is not touched by a single store.
 #pragma once
 
@@ -59,13 +63,12 @@ __device__ __forceinline__ void place_axis(uint32_t cq, int32_t cimg, float dx, 
   advance(*q, *img, f2i32(dx * inv_sx));
 }
 
-__global__ __launch_bounds__(256) void k_place_envs(const Derived* __restrict__ d, DevState st,
-                                                    ResetArgs a) {
+// Particle i of env: its placement with this reset ordinal and everything a
+// fresh engine has beside it (the body of k_place_envs and k_place_marked).
+__device__ __forceinline__ void place_particle(const Derived* __restrict__ d, const DevState& st,
+                                               const ResetArgs& a, int env, int i,
+                                               uint64_t ordinal) {
   const int N = st.n;
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long)a.n_listed * N) return;
-  const int k = (int)(t / N), i = (int)(t - (long)k * N);
-  const int env = a.envs[k];
   const size_t M = (size_t)st.m, gi = (size_t)env * N + i;
   const bool three_d = st.dims == 3;
 
@@ -85,8 +88,8 @@ __global__ __launch_bounds__(256) void k_place_envs(const Derived* __restrict__ 
     const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)env;
     u32x4 c;
     c.x = (uint32_t)i;
-    c.y = (uint32_t)a.ordinal;
-    c.z = (uint32_t)(a.ordinal >> 32);
+    c.y = (uint32_t)ordinal;
+    c.z = (uint32_t)(ordinal >> 32);
     c.w = kResetTag;
     const u32x4 r = philox4x32_10(c, k0, k1);
     float sn, cs;
@@ -158,6 +161,15 @@ __global__ __launch_bounds__(256) void k_place_envs(const Derived* __restrict__ 
   if (i == 0) a.cand_ok[env] = 0;
 }
 
+__global__ __launch_bounds__(256) void k_place_envs(const Derived* __restrict__ d, DevState st,
+                                                    ResetArgs a) {
+  const int N = st.n;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)a.n_listed * N) return;
+  const int k = (int)(t / N), i = (int)(t - (long)k * N);
+  place_particle(d, st, a, a.envs[k], i, a.ordinal);
+}
+
 // k_global's steepest descent over the listed envs.
 __global__ __launch_bounds__(1024) void k_global_envs(const Derived* __restrict__ d, DevState st,
                                                       Scratch sc,
@@ -199,6 +211,102 @@ __global__ __launch_bounds__(1024) void k_global3_envs(const Derived* __restrict
   block_global_run3(d, st, sc, env, n_steps, 0ull, lx, ly, lz, true, g, md, cnt, wave_sums, &pt,
                     par);
   save_forces_env(st, env, par);
+}
+
+// ---- swarm_engine_reset_marked: the envs a device mask marks.  Every grid is
+// the full one whatever the mask holds, so the launches can sit in a captured
+// graph; a thread (workgroup) of an unmarked env returns before any store
+// (before its first barrier).
+
+// Bit 63 of a marked reset's ordinal: apart from the host path's 0, 1, ...
+constexpr uint64_t kMarkedOrdinal = 1ull << 63;
+
+// k_place_envs over every env: env e draws with the ordinal 2^63 | counts[e],
+// the device-mask resets it has had.  k_count_marked bumps counts after this
+// launch: threads of one env sit in several workgroups here.
+__global__ __launch_bounds__(256) void k_place_marked(const Derived* __restrict__ d, DevState st,
+                                                      ResetArgs a,
+                                                      const uint8_t* __restrict__ mask,
+                                                      const uint32_t* __restrict__ counts) {
+  const int N = st.n;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)a.n_listed * N) return;
+  const int env = (int)(t / N), i = (int)(t - (long)env * N);
+  if (!mask[env]) return;
+  place_particle(d, st, a, env, i, kMarkedOrdinal | counts[env]);
+}
+
+__global__ __launch_bounds__(256) void k_count_marked(const uint8_t* __restrict__ mask,
+                                                      uint32_t* __restrict__ counts, int n_envs) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env < n_envs && mask[env]) counts[env] += 1u;
+}
+
+// k_global_envs with env = blockIdx.x, marked envs only.
+__global__ __launch_bounds__(1024) void k_global_marked(const Derived* __restrict__ d, DevState st,
+                                                        Scratch sc,
+                                                        const uint8_t* __restrict__ mask,
+                                                        int n_steps,
+                                                        const uint64_t* __restrict__ step_ctr,
+                                                        int lx, int ly, float g, float md) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ PairTables pt;
+  const int env = blockIdx.x;
+  if (!mask[env]) return;  // (the whole workgroup: before stage_pair_tables' barrier)
+  stage_pair_tables(d, &pt);
+  int32_t* wave_sums = reinterpret_cast<int32_t*>(smem);
+  int32_t* cnt = wave_sums + 16;
+  const int par = window_parity(step_ctr);
+  if (global_lds_extra_words(st.n, st.dims, 1 << (lx + ly)) && blockDim.x == 1024 && d->periodic)
+    block_env_run(d, st, env, n_steps, 0ull, lx, ly, true, g, md, cnt, wave_sums,
+                  cnt + (1 << (lx + ly)) + 1, &pt, par, PlainEnvPath{});
+  else
+    block_global_run(d, st, sc, env, n_steps, 0ull, lx, ly, true, g, md, cnt, wave_sums, &pt,
+                     par);
+  save_forces_env(st, env, par);
+}
+
+// k_global3_envs likewise.
+__global__ __launch_bounds__(1024) void k_global3_marked(const Derived* __restrict__ d,
+                                                         DevState st, Scratch sc,
+                                                         const uint8_t* __restrict__ mask,
+                                                         int n_steps,
+                                                         const uint64_t* __restrict__ step_ctr,
+                                                         int lx, int ly, int lz, float g,
+                                                         float md) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ PairTables pt;
+  const int env = blockIdx.x;
+  if (!mask[env]) return;
+  stage_pair_tables(d, &pt);
+  int32_t* wave_sums = reinterpret_cast<int32_t*>(smem);
+  int32_t* cnt = wave_sums + 16;
+  const int par = window_parity(step_ctr);
+  block_global_run3(d, st, sc, env, n_steps, 0ull, lx, ly, lz, true, g, md, cnt, wave_sums, &pt,
+                    par);
+  save_forces_env(st, env, par);
+}
+
+// swarm_field_history_marked: the fixed-point position history of k_field
+// (hist_q, hist_img [3][E * A], slot env * A + agent) <- the current q / img
+// for the agents of marked envs, as k_field's init_only does for every env.
+__global__ __launch_bounds__(256) void k_field_history_marked(DevState st,
+                                                              const uint8_t* __restrict__ mask,
+                                                              const int32_t* __restrict__ agents,
+                                                              int n_agents, int n_envs,
+                                                              uint32_t* __restrict__ hq,
+                                                              int32_t* __restrict__ himg) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int A = n_agents * n_envs;
+  if (t >= A) return;
+  const int e = t / n_agents, ai = t - e * n_agents;
+  if (!mask[e]) return;
+  const size_t M = (size_t)st.m, gi = (size_t)e * st.n + agents[ai];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    hq[(size_t)a * A + t] = a < st.dims ? st.q[a * M + gi] : 0u;
+    himg[(size_t)a * A + t] = a < st.dims ? st.img[a * M + gi] : 0;
+  }
 }
 
 }  // namespace swarm

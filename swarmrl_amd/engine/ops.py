@@ -131,6 +131,32 @@ def field_distance(native, n_envs: int, agent_idx: torch.Tensor, source, box_sca
     return d_cur, d_prev
 
 
+def field_history_marked(native, mask: torch.Tensor, agent_idx: torch.Tensor,
+                         hist_q: torch.Tensor, hist_img: torch.Tensor) -> None:
+    """history <- current position for the agents of the envs mask marks
+    (uint8 [E] device; swarm_field_history_marked, capturable); the history of
+    the other envs is not stored to."""
+    A = int(agent_idx.numel())
+    if A == 0:
+        return
+    native.bind_stream()
+    native.call("swarm_field_history_marked", mask.data_ptr(), agent_idx.data_ptr(), A,
+                hist_q.data_ptr(), hist_img.data_ptr())
+
+
+def device_history(holder, view):
+    """The (hq, hi) device history of a field observable / task for this
+    view's engine, taking over a history snapshotted on the list path."""
+    if holder._dev_hist is None and getattr(holder, "_pending", None) is not None:
+        if holder._pending[0] == id(view.engine):
+            holder._dev_hist = (holder._pending[0], *history_tensors(
+                holder._pending[1], holder._pending[2], view.device))
+        holder._pending = None
+    if holder._dev_hist is None or holder._dev_hist[0] != id(view.engine):
+        raise ValueError(f"{type(holder).__name__} was not initialised for this engine")
+    return holder._dev_hist[1], holder._dev_hist[2]
+
+
 # ------------------------------------------------------------ list path
 class _PointsEngine:
     """A scratch single-env engine that holds an arbitrary point set (2-D, or
@@ -475,7 +501,7 @@ def adam_args(optimizer, layers):
 def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torch.Tensor,
                    rewards: torch.Tensor, layers, gamma: float, lambda_: float,
                    clip_eps: float, entropy_coef: float, out: torch.Tensor = None,
-                   adam=None, workspaces: dict = None) -> torch.Tensor:
+                   adam=None, workspaces: dict = None, dones: torch.Tensor = None) -> torch.Tensor:
     """
     The gradient of one PPO epoch (swarm_ppo_epoch_grad): features [T, S, d]
     fp32, actions [T, S] int64, old_logp / rewards [T, S] fp32 (all device),
@@ -492,15 +518,27 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     holds a workspace's pointer never replays into freed memory); without
     one every call takes a fresh zeroed buffer (a module-wide
     single-entry cache freed a buffer another loss's graph still used).
+    dones: uint8 [T, E] device, E dividing S (an env's flag covers its S / E
+    agent columns): the advantages do not bootstrap across a step after which
+    the env was reset (the *_ep siblings of the three entries).
     """
     T, S = int(actions.shape[0]), int(actions.shape[1])
+    done_args = ()
+    if dones is not None:
+        if (dones.dtype != torch.uint8 or dones.dim() != 2 or int(dones.shape[0]) != T
+                or int(dones.shape[1]) < 1 or S % int(dones.shape[1]) != 0
+                or dones.device != actions.device):
+            raise ValueError("dones must be a uint8 [T, E] tensor on the data's device, "
+                             "E dividing S")
+        dones = dones.contiguous()
+        done_args = (dones.data_ptr(), S // int(dones.shape[1]))
     x = features.reshape(T * S, -1).to(torch.float32).contiguous()
     d_in = int(x.shape[1])
     if len(layers) > 6:
         if adam is not None:
             raise ValueError("the fused Adam step covers the six-layer network only")
         return _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lambda_,
-                                    clip_eps, entropy_coef, out, workspaces)
+                                    clip_eps, entropy_coef, out, workspaces, done_args)
     w1, b1, wa, ba, wc, bc = layers
     hidden, k = int(w1.shape[0]), int(wa.shape[0])
     dev = x.device
@@ -523,25 +561,28 @@ def ppo_epoch_grad(features: torch.Tensor, actions: torch.Tensor, old_logp: torc
     rew = rewards.to(torch.float32).contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
     if adam is not None:  # the optimizer step fused into the epoch (swarm_ppo_epoch_step)
-        _capi.check(lib.swarm_ppo_epoch_step(
+        fn = lib.swarm_ppo_epoch_step_ep if done_args else lib.swarm_ppo_epoch_step
+        _capi.check(fn(
             x.data_ptr(), T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(), hidden, k,
             ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
             ctypes.c_float(entropy_coef), ctypes.byref(adam), ws.data_ptr(), nbytes,
-            grad.data_ptr(), ctypes.c_void_p(stream)))
+            grad.data_ptr(), ctypes.c_void_p(stream), *done_args))
         return grad
-    _capi.check(lib.swarm_ppo_epoch_grad(
+    fn = lib.swarm_ppo_epoch_grad_ep if done_args else lib.swarm_ppo_epoch_grad
+    _capi.check(fn(
         x.data_ptr(), T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(),
         w1.data_ptr(), b1.data_ptr(), hidden, wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
         bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
         ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
-        ctypes.c_void_p(stream)))
+        ctypes.c_void_p(stream), *done_args))
     return grad
 
 
 def _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lambda_, clip_eps,
-                         entropy_coef, out, workspaces):
+                         entropy_coef, out, workspaces, done_args=()):
     """ppo_epoch_grad for the deep MLP (swarm_ppo_deep_epoch_grad): x [T * S, d]
-    fp32 contiguous; layers = (w1, b1, ..., wL, bL, wa, ba, wc, bc)."""
+    fp32 contiguous; layers = (w1, b1, ..., wL, bL, wa, ba, wc, bc).
+    done_args: (dones pointer, per_env) for the _ep sibling."""
     d_in = int(x.shape[1])
     hidden = layers[:-4]
     wa, ba, wc, bc = layers[-4:]
@@ -569,13 +610,14 @@ def _ppo_deep_epoch_grad(x, T, S, actions, old_logp, rewards, layers, gamma, lam
     olp = old_logp.to(torch.float32).contiguous()
     rew = rewards.to(torch.float32).contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(lib.swarm_ppo_deep_epoch_grad(
+    fn = lib.swarm_ppo_deep_epoch_grad_ep if done_args else lib.swarm_ppo_deep_epoch_grad
+    _capi.check(fn(
         x.data_ptr(), T, S, d_in, acts.data_ptr(), olp.data_ptr(), rew.data_ptr(), len(ws_),
         ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wp, ctypes.c_void_p),
         ctypes.cast(bp, ctypes.c_void_p), wa.data_ptr(), ba.data_ptr(), k, wc.data_ptr(),
         bc.data_ptr(), ctypes.c_float(gamma), ctypes.c_float(lambda_), ctypes.c_float(clip_eps),
         ctypes.c_float(entropy_coef), ws.data_ptr(), nbytes, grad.data_ptr(),
-        ctypes.c_void_p(stream)))
+        ctypes.c_void_p(stream), *done_args))
     return grad
 
 

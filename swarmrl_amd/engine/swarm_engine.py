@@ -312,6 +312,10 @@ class SwarmEngine(Engine):
         # groups of reset_envs; _reset_plan_set: the library holds the plan
         self._reset_groups: typing.List[tuple] = []
         self._reset_plan_set = False
+        # set_auto_reset: (done_fn, remove_overlap); _no_done: the all-zero
+        # mask recorded after a chunk that ends at a write point only
+        self._auto_reset = None
+        self._no_done = None
         self._native: _NativeEngine = None
         self._host_cache = None
         self._view = None
@@ -1184,20 +1188,76 @@ class SwarmEngine(Engine):
                 torch.cuda.current_stream().wait_stream(self._prebuild_pending[0])
             self._prebuild_pending = None
         self._native.bind_stream()
-        if not self._reset_plan_set:
-            pos, dirs, groups = self._reset_plan()
-            arr = (_capi.SwarmResetGroup * max(1, len(groups)))()
-            for k, (first, count, centre, radius) in enumerate(groups):
-                arr[k].first, arr[k].count, arr[k].radius = first, count, radius
-                for a in range(3):
-                    arr[k].centre[a] = float(centre[a])
-            self._native.call("swarm_engine_set_reset_plan", pos.ctypes.data, dirs.ctypes.data,
-                              ctypes.cast(arr, ctypes.c_void_p), len(groups))
-            self._reset_plan_set = True
+        self._ensure_reset_plan()
         self._native.call("swarm_engine_reset_envs",
                           None if mask is None else mask.ctypes.data,
                           1000 if remove_overlap else 0, 0.1, 0.1)
         self._host_cache = None
+
+    def _ensure_reset_plan(self):
+        """Hand the reset plan to the library on first use (uploads and
+        synchronises: not under a stream capture)."""
+        if self._reset_plan_set:
+            return
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the reset plan cannot be set under a stream capture: call "
+                               "reset_envs_where (or reset_envs) once before capturing")
+        pos, dirs, groups = self._reset_plan()
+        arr = (_capi.SwarmResetGroup * max(1, len(groups)))()
+        for k, (first, count, centre, radius) in enumerate(groups):
+            arr[k].first, arr[k].count, arr[k].radius = first, count, radius
+            for a in range(3):
+                arr[k].centre[a] = float(centre[a])
+        self._native.call("swarm_engine_set_reset_plan", pos.ctypes.data, dirs.ctypes.data,
+                          ctypes.cast(arr, ctypes.c_void_p), len(groups))
+        self._reset_plan_set = True
+
+    def _validate_mask(self, mask):
+        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8
+                and tuple(mask.shape) == (self.n_envs,) and mask.is_contiguous()
+                and mask.device == torch.device(self.device)):
+            raise ValueError(f"mask must be a contiguous torch.uint8 tensor of shape "
+                             f"[{self.n_envs}] on {self.device}")
+
+    def reset_envs_where(self, mask: torch.Tensor, remove_overlap: bool = True):
+        """reset_envs for the envs a device mask marks (uint8 [n_envs] on the
+        engine's device, non-zero: reset), with no host copy and no
+        synchronisation: the call can be captured into a graph and replayed
+        with other mask contents.  A marked env gets what reset_envs gives it;
+        its draws are keyed by the number of marked resets that env has had
+        (reset_counts), so the k-th reset of an env does not depend on the
+        other envs.  The reset plan is set on first use, which cannot happen
+        under a capture."""
+        self._validate_reset()
+        self._validate_mask(mask)
+        if self._prebuild_pending is not None:  # a build forked from the old positions
+            if self._prebuild_pending[0] != "ride":
+                torch.cuda.current_stream().wait_stream(self._prebuild_pending[0])
+            self._prebuild_pending = None
+        self._native.bind_stream()
+        self._ensure_reset_plan()
+        self._native.call("swarm_engine_reset_marked", mask.data_ptr(),
+                          1000 if remove_overlap else 0, 0.1, 0.1)
+        self._host_cache = None
+
+    def reset_counts(self) -> np.ndarray:
+        """Per env, the resets reset_envs_where has given it (synchronises)."""
+        out = np.zeros(self.n_envs, np.uint32)
+        if self._native is not None:
+            self._native.bind_stream()
+            self._native.call("swarm_engine_reset_counts", out.ctypes.data)
+        return out
+
+    def set_auto_reset(self, done_fn, remove_overlap: bool = True):
+        """Let envs end their episodes on their own: at every slice boundary
+        integrate() calls done_fn(view) -> uint8 [n_envs] device tensor (no
+        host synchronisation), hands it to force_model.record_dones, resets
+        the marked envs (reset_envs_where) and lets the force model
+        re-initialise their histories (reinitialize_envs).  None switches it
+        off.  Needs a device-capable force model."""
+        self._auto_reset = None if done_fn is None else (done_fn, bool(remove_overlap))
+        if done_fn is not None and self._no_done is None:  # (not under a later capture)
+            self._no_done = torch.zeros(self.n_envs, dtype=torch.uint8, device=self.device)
 
     # --------------------------------------------------------- trajectory
     def _init_h5_output(self):
@@ -1538,6 +1598,9 @@ class SwarmEngine(Engine):
         self._ride_along = bool(device_path and self.ride_along_build and
                                 getattr(force_model, "absorbs_build", lambda: False)())
         old_slice_idx = self.slice_idx
+        auto_reset = self._auto_reset
+        if auto_reset is not None and not device_path:
+            raise ValueError("auto-reset needs a device-capable force model")
 
         while self.step_idx < self.params.steps_per_slice * (old_slice_idx + n_slices):
             if self.step_idx == self.params.steps_per_write_interval * self.write_idx:
@@ -1567,8 +1630,11 @@ class SwarmEngine(Engine):
             steps_to_next = min(steps_to_next_write, steps_to_next_slice)
 
             nxt = self.step_idx + steps_to_next
+            at_slice_end = nxt == self.params.steps_per_slice * self.slice_idx
+            # (auto-reset: a reset may replace the positions the next slice's
+            # build would fork from; it is built at that slice's start)
             early = (device_path and self.overlap_build and self.early_fork
-                     and nxt == self.params.steps_per_slice * self.slice_idx
+                     and auto_reset is None and at_slice_end
                      and nxt < self.params.steps_per_slice * (old_slice_idx + n_slices))
             # the reward launch of a slice with a ride-along build can carry
             # this chunk's last check beside the build's first stage
@@ -1580,10 +1646,28 @@ class SwarmEngine(Engine):
                 self._prebuild(self.params.steps_per_slice)
             if force_model is not None:
                 force_model.calc_reward(self.swarm_view() if device_path else self.colloids)
+            if auto_reset is not None:
+                self._auto_reset_step(force_model, auto_reset, at_slice_end)
             self.step_idx += steps_to_next
         # a check no reward launch carried: host-side state must not outlive
         # this call (a stream capture around it would replay without the check)
         self._native.call("swarm_engine_flush_check")
+
+    def _auto_reset_step(self, force_model, auto_reset, at_slice_end: bool):
+        """After a chunk's reward (computed from the pre-reset state): at a
+        slice boundary the done mask, its record, the reset of the marked envs
+        and their histories from the fresh start; after a chunk that ends at a
+        write point only an all-zero record, one per reward."""
+        if not at_slice_end:
+            force_model.record_dones(self._no_done)
+            return
+        done_fn, remove_overlap = auto_reset
+        view = self.swarm_view()
+        mask = done_fn(view)
+        self._validate_mask(mask)
+        force_model.record_dones(mask)
+        self.reset_envs_where(mask, remove_overlap=remove_overlap)
+        force_model.reinitialize_envs(self.swarm_view(), mask)
 
     def finalize(self):
         """Write the last trajectory chunk (espresso.py:1310-1318)."""

@@ -108,5 +108,20 @@ class ForceFunction:
         for agent in self.agents:
             self.agents[agent].calc_reward(colloids=colloids, external_reward=external_reward)
 
+    def record_dones(self, mask) -> None:
+        """An auto-reset engine's done mask of the last transition (uint8 [E]
+        device tensor), to every agent that records one."""
+        for agent in self.agents.values():
+            fn = getattr(agent, "record_dones", None)
+            if fn is not None:
+                fn(mask)
+
+    def reinitialize_envs(self, view, mask) -> None:
+        """After the reset of the marked envs: their per-env histories."""
+        for agent in self.agents.values():
+            fn = getattr(agent, "reinitialize_envs", None)
+            if fn is not None:
+                fn(view, mask)
+
 
 __all__ = ["ForceFunction"]

@@ -7,6 +7,8 @@ R = ExpectedReturns(rewards) (discounted, standardised per agent); one
 gradient step per episode.
 """
 
+import warnings
+
 import torch
 import torch.nn.functional as F
 
@@ -19,6 +21,7 @@ class PolicyGradientLoss(Loss):
         self.value_function = value_function if value_function is not None else ExpectedReturns()
         self.n_particles = None
         self.n_time_steps = None
+        self._warned_dones = False
 
     def _calculate_loss(self, network, feature_data, action_indices, rewards):
         """The reference's _calculate_loss (:47-106): actor term on the
@@ -37,6 +40,10 @@ class PolicyGradientLoss(Loss):
         return actor_loss + critic_loss
 
     def compute_loss(self, network, episode_data):
+        if len(getattr(episode_data, "dones", ())) > 0 and not self._warned_dones:
+            self._warned_dones = True
+            warnings.warn("PolicyGradientLoss / ExpectedReturns ignore the trajectory's dones: "
+                          "returns are discounted across episode ends", stacklevel=2)
         dev = network.device
         features = _stack(episode_data.features, dev).float()
         actions = _stack(episode_data.actions, dev).long()

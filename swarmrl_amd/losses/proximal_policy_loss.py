@@ -9,7 +9,9 @@ actor-critic MLP, each epoch's gradient comes from the fused kernels of
 swarm_ppo_epoch_grad (csrc/swarm_ppo.cuh), for a deep one (2 or 3 hidden
 layers) from swarm_ppo_deep_epoch_grad (csrc/swarm_deep.cuh), and torch's
 optimizer takes the step; otherwise torch autograd differentiates
-_calculate_loss.
+_calculate_loss.  An episode with dones (an auto-reset engine's: envs that
+were reset inside it) takes the done-aware GAE on either path
+(swarm_ppo_epoch_grad_ep and its siblings on the fused one).
 """
 
 import os
@@ -46,13 +48,22 @@ class ProximalPolicyLoss(Loss):
         self.entropy_coefficient = entropy_coefficient
         self.eps = 1e-8
 
-    def _calculate_loss(self, network, feature_data, action_indices, rewards, old_log_probs):
+    def _calculate_loss(self, network, feature_data, action_indices, rewards, old_log_probs,
+                        dones=None):
+        """dones: uint8 [T, E] (an auto-reset engine's trajectory), an env's
+        flag covering its S / E agent columns; None: no episode ended inside."""
         obs_ndim = feature_data.ndim - 2
         new_logits, predicted_values = network(feature_data, obs_ndim=obs_ndim)
         predicted_values = predicted_values.squeeze(-1)
         # as in the reference (:101-124), only the normalised advantages are
         # held constant: the returns R = A + V stay differentiable in V
-        advantages, returns = self.value_function(rewards=rewards, values=predicted_values)
+        if dones is None:
+            advantages, returns = self.value_function(rewards=rewards, values=predicted_values)
+        else:
+            per_env = rewards.shape[1] // dones.shape[1]
+            advantages, returns = self.value_function(
+                rewards=rewards, values=predicted_values,
+                dones=dones.repeat_interleave(per_env, dim=1))
         advantages = advantages.detach()
         new_probabilities = torch.softmax(new_logits, dim=-1)
         entropy = self.sampling_strategy.compute_entropy(new_probabilities)
@@ -79,10 +90,19 @@ class ProximalPolicyLoss(Loss):
             old_log_probs = old_log_probs.reshape(T, E * A)
             features = features.reshape(T, E * A, *features.shape[3:])
             rewards = rewards.reshape(rewards.shape[0], E * A)
+        # an auto-reset engine's trajectory: where envs were reset, [T, E]
+        dones = None
+        if len(getattr(episode_data, "dones", ())) > 0:
+            dones = _stack(episode_data.dones, dev).to(torch.uint8).contiguous()
+            if (dones.ndim != 2 or dones.shape[0] != rewards.shape[0]
+                    or rewards.shape[1] % dones.shape[1] != 0):
+                raise ValueError("dones must stack to [T, E], one entry per reward, with E "
+                                 "dividing the agent columns")
         layers = self._fused_layers(network, features, actions)
         if layers is not None:
             features = features.reshape(features.shape[0], features.shape[1], -1).contiguous()
-            if self._graph_epochs(network, layers, features, actions, old_log_probs, rewards):
+            if self._graph_epochs(network, layers, features, actions, old_log_probs, rewards,
+                                  dones):
                 return
         for _ in range(self.n_epochs):
             if layers is not None:
@@ -90,13 +110,15 @@ class ProximalPolicyLoss(Loss):
                                           self.value_function.gamma,
                                           self.value_function.lambda_, self.epsilon,
                                           self.entropy_coefficient,
-                                          workspaces=self._workspaces())
+                                          workspaces=self._workspaces(), dones=dones)
                 network.apply_gradients(layers, grad)
                 continue
-            loss = self._calculate_loss(network, features, actions, rewards, old_log_probs)
+            loss = self._calculate_loss(network, features, actions, rewards, old_log_probs,
+                                        dones)
             network.update_model(loss)
 
-    def _graph_epochs(self, network, layers, features, actions, old_log_probs, rewards):
+    def _graph_epochs(self, network, layers, features, actions, old_log_probs, rewards,
+                      dones=None):
         """
         The n_epochs fused steps (gradient kernels + the optimizer's step) as
         one captured HIP graph, replayed per episode with the episode's data
@@ -124,7 +146,7 @@ class ProximalPolicyLoss(Loss):
         # every hyper-parameter the fused step bakes into its captured
         # arguments (betas / eps were missing)
         sig = (adam is not None, id(network), id(opt), tuple(features.shape),
-               tuple(actions.shape),
+               tuple(actions.shape), None if dones is None else tuple(dones.shape),
                tuple((float(g["lr"]), tuple(float(b) for b in g.get("betas", ())),
                       float(g.get("eps", 0.0)), float(g.get("weight_decay", 0.0)),
                       bool(g.get("amsgrad", False)), bool(g.get("maximize", False)))
@@ -142,6 +164,7 @@ class ProximalPolicyLoss(Loss):
             act = actions.to(torch.int64).clone()
             olp = old_log_probs.to(torch.float32).clone()
             rew = rewards.to(torch.float32).clone()
+            dn = None if dones is None else dones.clone()
             grad = torch.zeros(sum(p.numel() for p in layers), dtype=torch.float32,
                                device=features.device)
             off = 0
@@ -152,7 +175,7 @@ class ProximalPolicyLoss(Loss):
                     self.value_function.lambda_, self.epsilon, self.entropy_coefficient)
             ws = self._workspaces()
             # sizes the workspace outside the capture
-            ops.ppo_epoch_grad(*args, out=grad, workspaces=ws)
+            ops.ppo_epoch_grad(*args, out=grad, workspaces=ws, dones=dn)
             torch.cuda.synchronize(features.device)
             graph = torch.cuda.CUDAGraph()
             # (thread-local: a process group's watchdog thread may query
@@ -160,13 +183,15 @@ class ProximalPolicyLoss(Loss):
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 for _ in range(self.n_epochs):
                     if adam is not None:
-                        ops.ppo_epoch_grad(*args, out=grad, adam=adam, workspaces=ws)
+                        ops.ppo_epoch_grad(*args, out=grad, adam=adam, workspaces=ws, dones=dn)
                     else:
-                        ops.ppo_epoch_grad(*args, out=grad, workspaces=ws)
+                        ops.ppo_epoch_grad(*args, out=grad, workspaces=ws, dones=dn)
                         opt.step()
-            cache = self._ppo_graph = {"sig": sig, "graph": graph, "inputs": (x, act, olp, rew),
-                                       "grad": grad}
-        x, act, olp, rew = cache["inputs"]
+            cache = self._ppo_graph = {"sig": sig, "graph": graph,
+                                       "inputs": (x, act, olp, rew, dn), "grad": grad}
+        x, act, olp, rew, dn = cache["inputs"]
+        if dn is not None:
+            dn.copy_(dones)
         x.copy_(features)
         act.copy_(actions)
         olp.copy_(old_log_probs)

@@ -77,6 +77,12 @@ class ConcentrationField(Observable):
         # check of the reference behaves the same for both paths
         self._historic_positions = {"__device__": True}
 
+    def reinitialize_envs(self, view, mask):
+        """The marked envs' history <- their current (fresh) positions."""
+        hq, hi = ops.device_history(self, view)
+        ops.field_history_marked(view.engine._native, mask,
+                                 view.indices_of_type(self.particle_type), hq, hi)
+
     # ---------------------------------------------------------- compute
     def _delta(self, d_cur, d_prev):
         return self.scale_factor * (self.decay_fn(d_cur) - self.decay_fn(d_prev))

@@ -34,6 +34,10 @@ class MultiSensing(Observable):
         for item in self.observables:
             item.initialize(colloids)
 
+    def reinitialize_envs(self, view, mask):
+        for item in self.observables:
+            item.reinitialize_envs(view, mask)
+
     def compute_observable(self, colloids):
         if is_view(colloids):
             parts = [o.compute_observable(colloids) for o in self.observables]

@@ -21,6 +21,11 @@ class Observable:
         """Initialise with the starting positions (default: nothing to do)."""
         pass
 
+    def reinitialize_envs(self, view, mask):
+        """Re-initialise the history of the envs mask marks (uint8 [E] device
+        tensor) after their reset (default: no history, nothing to do)."""
+        pass
+
     def get_colloid_indices(self, colloids, p_type: int = None) -> List[int]:
         """Indices of the colloids of one type (observable.py:40-68)."""
         if p_type is None:

@@ -47,6 +47,13 @@ class ParticleSensing(Observable):
         for i, value in zip(self.get_colloid_indices(colloids), field):
             self.historical_field[str(colloids[i].id)] = float(value)
 
+    def reinitialize_envs(self, view, mask):
+        """The marked envs' field history <- the field of their fresh start."""
+        if self._dev_hist is None or self._dev_hist[0] != id(view.engine):
+            raise ValueError(f"{type(self).__name__} was initialised for another engine")
+        hist = torch.where(mask.bool().unsqueeze(-1), self._field(view), self._dev_hist[1])
+        self._dev_hist = (self._dev_hist[0], hist)
+
     def compute_observable(self, colloids):
         """scale * (field - previous field): (A, 1), or [E, A, 1] on the device."""
         if self.historical_field == {}:

@@ -24,6 +24,10 @@ class MultiTasking(Task):
         for item in self.tasks:
             item.initialize(colloids)
 
+    def reinitialize_envs(self, view, mask):
+        for item in self.tasks:
+            item.reinitialize_envs(view, mask)
+
     def __call__(self, colloids):
         if is_view(colloids):
             rewards = None

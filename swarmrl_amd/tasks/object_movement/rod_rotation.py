@@ -109,6 +109,10 @@ class RotateRod(Task):
                     1 if self.partition else 0, out.data_ptr())
         return out
 
+    def reinitialize_envs(self, view, mask):
+        raise NotImplementedError("RotateRod cannot re-initialise single envs: an engine with a "
+                                  "rod cannot reset in place")
+
     # ------------------------------------------------------------ list path
     def initialize(self, colloids):
         """The rod's director now is the historic one (all rod particles

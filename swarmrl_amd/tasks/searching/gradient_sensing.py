@@ -64,6 +64,12 @@ class GradientSensing(Task):
                 position = np.copy(item.pos) / self.box_length
                 self._historic_positions[str(index)] = position
 
+    def reinitialize_envs(self, view, mask):
+        """The marked envs' history <- their current (fresh) positions."""
+        hq, hi = ops.device_history(self, view)
+        ops.field_history_marked(view.engine._native, mask,
+                                 view.indices_of_type(self.particle_type), hq, hi)
+
     def change_source(self, new_source: np.ndarray):
         self.source = new_source
         self._source_raw = np.asarray(new_source, dtype=float) * np.asarray(self.box_length)

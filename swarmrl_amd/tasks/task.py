@@ -27,6 +27,11 @@ class Task:
     def initialize(self, colloids):
         pass
 
+    def reinitialize_envs(self, view, mask):
+        """Re-initialise the history of the envs mask marks (uint8 [E] device
+        tensor) after their reset (default: no history, nothing to do)."""
+        pass
+
     def get_colloid_indices(self, colloids, p_type: int = None) -> List[int]:
         if p_type is None:
             p_type = self.particle_type

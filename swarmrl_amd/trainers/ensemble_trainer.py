@@ -79,6 +79,8 @@ class EnsembleTrainer(ContinuousTrainer):
         for agent in self.agents.values():
             if not isinstance(agent, ActorCriticAgent):
                 continue
+            # (GeneticTraining's generations run through here as well)
+            self._refuse_dones(agent, type(self).__name__)
             rewards, killed = self._update_agent(agent)
             total += member_mean_rewards(rewards, self.n_members)
             stop = stop or _is_killed(killed)

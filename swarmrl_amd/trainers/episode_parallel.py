@@ -64,6 +64,7 @@ class _ReplicatedUpdate:
     def _update_agent(self, agent):
         if not getattr(agent, "train", True) or not hasattr(agent, "loss"):
             return agent.update_agent()
+        self._refuse_dones(agent, type(self).__name__)
         episode = rollout.gather_episode(agent.trajectory, group=self.group,
                                          env_counts=self.env_counts)
         self._episodes += 1

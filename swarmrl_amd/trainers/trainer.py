@@ -74,6 +74,15 @@ class Trainer:
             stop = stop or _is_killed(killed)
         return ForceFunction(agents=self.agents), np.array(total), stop
 
+    @staticmethod
+    def _refuse_dones(agent, who: str):
+        """Trainers whose update does not cut the advantage estimate at episode
+        ends refuse a trajectory that has some (an auto-reset engine's)."""
+        traj = getattr(agent, "trajectory", None)
+        if traj is not None and len(getattr(traj, "dones", ())) > 0:
+            raise ValueError(f"{who} does not support episodes that end inside a trajectory "
+                             "(SwarmEngine.set_auto_reset): its update ignores dones")
+
     def _update_agent(self, agent):
         """One learning agent's update after an episode (the episode-parallel
         trainers gather the episode over the ranks first)."""

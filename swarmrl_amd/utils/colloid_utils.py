@@ -18,6 +18,9 @@ class TrajectoryInformation:
     log_probs: list = field(default_factory=list)
     rewards: list = field(default_factory=list)
     killed: bool = False
+    # auto-reset engines: per reward, the uint8 [E] mask of the envs that were
+    # reset after that transition (empty: no episode ended inside)
+    dones: list = field(default_factory=list)
 
 
 def compute_torque_partition_on_rod(colloid_positions, rod_positions, rod_directions):
