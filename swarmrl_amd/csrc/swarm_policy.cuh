@@ -25,7 +25,10 @@
 // group advances it after every thread has read it, so a captured HIP graph
 // draws fresh numbers on every replay without any cross-workgroup atomics.
 // Parity with the reference is statistical (its draws come from JAX's
-// threefry), see tests.
+// threefry); the draws themselves are pinned to this specification
+// (key = (seed lo, seed hi); word q of block b is action 4 b + q; exploration
+// block: counter word 0x80000000, word 0 the switch, word 1 the random
+// action) by tests/sampler_ref.py and tests/test_gpu_sampler.py.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,8 +43,15 @@ constexpr int kMlpMaxIn = 16;      // fused MLP: observable features per agent
 constexpr int kMlpMaxHidden = 256;  // LDS: hidden x 36 floats <= 36 KB
 constexpr int kMlpMaxActions = 16;
 
+// (0, 1]: the 2^-24 grid offset by 2^-25 while r >> 8 < 2^23; above that the
+// sum is not representable in fp32 and ties to even (a 2^-23 grid), and
+// r >> 8 == 0xFFFFFF, once in 2^24 draws, gives exactly 1.0f.  In
+// sample_logits that is -logf(1.0f) = -0.0f, logf(-0.0f) = -inf: a Gumbel
+// score of +inf, the action is taken whatever its logit (the limit of
+// Gumbel-max), and logp, computed from the logits alone, stays finite.
+// Every stream depends on this function as written (tests/sampler_ref.py).
 __device__ __forceinline__ float uniform24(uint32_t r) {
-  return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1), 2^-24 grid
+  return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-08f;
 }
 
 struct Sampled {
