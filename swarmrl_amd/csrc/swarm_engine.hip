@@ -10,6 +10,8 @@
 //                   k_global also runs steepest descent (espresso.py:1161-1168).
 //   observables     swarm_observe.cuh: k_grid_build, k_vision*, k_field*,
 //                   k_pairs, the trajectory ring.
+//   packing         swarm_pack.h (plain C++17): the build/run contract -- packing
+//                   classes, their layout in waves, the pair and class words.
 //   planning        swarm_plan.h over swarm_sizes.h (plain C++17): the checks,
 //                   cell grids, path choices and buffer sizes an engine fixes
 //                   at creation, one pure function (swarm::plan_engine).

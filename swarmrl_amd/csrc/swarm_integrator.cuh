@@ -37,6 +37,7 @@
 #include "../../include/swarmrl_amd.h"
 #include "swarm_device.cuh"
 #include "swarm_potential.cuh"
+#include "swarm_pack.h"
 #include "swarm_sizes.h"
 
 // Sub-step schedule of the run kernels (round 6): off-chain work placed in
@@ -64,14 +65,13 @@ constexpr int kRunMinBlocks = 5;
 #endif
 constexpr int kRunMinBlocksPot = SWARM_POT_MIN_BLOCKS;
 // (capacities and LDS sizes shared with the host's planning: swarm_sizes.h)
-constexpr int kBigMark = -0x40000000;  // cbase of a big cluster's root
 // multi-workgroup build (k_mwb_*): sc.bmisc layout per env
 constexpr int kBmMisc = 0;     // [16]: 0 overflow, 1 waves, 2 pair overflow, 3 free lanes,
                                // 4 big members, 6 big pairs, 8 / 9 tickets
-constexpr int kBmClass = 16;   // [68] cluster count per class
-constexpr int kBmWave = 84;    // [68] first wave of a class
-constexpr int kBmFree = 152;   // [68] first free tail lane of a class (singletons)
-constexpr uint32_t kMwbBig = 0x80000000u;  // B of a big cluster's root: kMwbBig | first member
+constexpr int kBmClass = 16;   // the three class tables (swarm_pack.h, pack_tables)
+constexpr int kBmWave = kBmClass + kPackTableWords;
+constexpr int kBmFree = kBmWave + kPackTableWords;
+static_assert(kBmFree + kPackTableWords <= kBmWords, "sc.bmisc holds the class tables");
 
 constexpr float kAngInvScale = 683565275.57643158f;  // 2^32 / (2 pi)
 
@@ -205,14 +205,14 @@ struct Scratch {
   int32_t* root;      // [M] cluster id (root particle)
   int32_t* slot_of;   // [M] wave slot of a particle
   int32_t* perm;      // [E][S] particle of a slot (-1: idle lane)
-  uint32_t* pairs;    // [E][wmax][kPairsPerWave]: lane a | lane b << 6 | species pair << 12
+  uint32_t* pairs;    // [E][wmax][kPairsPerWave] wave pair words (swarm_pack.h)
   int32_t* wave_npairs;  // [E][wmax]
   float* disp;        // [M] max displacement over the window
   float* bdir3;       // [3][M] window-start directors (3-D cluster path)
   int32_t* env_waves; // [E]
   int32_t* fallback;  // [E]
   int32_t* big_list;  // [E][kBigMax] particles of the env's big clusters (member order)
-  uint32_t* big_pairs;  // [E][kBigPairs] member a | member b << 10 | species pair << 20
+  uint32_t* big_pairs;  // [E][kBigPairs] big-cluster pair words (swarm_pack.h)
   int32_t* big_n;     // [E] members
   int32_t* big_np;    // [E] pairs
   // colloids that moved >= skin / 2 in the window (appended by the run
@@ -376,17 +376,6 @@ __device__ __forceinline__ float pair_disp(uint32_t qj, int32_t ij, uint32_t qi,
   return (float)dq * sx;
 }
 
-// floor(n / d) for 0 <= n < 2^20 and 1 <= d < 2^20: a float reciprocal
-// estimate (within one of the quotient) and one correction, instead of the
-// compiler's ~40-instruction integer division (the cluster build's packing
-// divides per cluster: 64 / s, r / per).
-__device__ __forceinline__ int udiv_small(int n, int d) {
-  int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-  const int r = n - q * d;
-  q += (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-  return q;
-}
-
 // Inclusive prefix sum over a wave's 64 lanes on the DPP network: row
 // shifts 1, 2, 4, 8 scan each 16-lane row, the gfx9 row broadcasts 15 and 31
 // carry rows into the next ones.  VALU only (no ds_bpermute round trip per
@@ -399,6 +388,97 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
   return v;
+}
+
+// ---- the device half of the packing contract (swarm_pack.h), shared by the
+// cluster builds
+// The classes laid out in waves by one full wave, lane w - 1 for class w with
+// cnt clusters: that lane gets the class's free-lane base and first wave;
+// lane 63 alone also holds the env's waves and (every lane) the free lanes
+// the singletons may take, 0 unless fill.
+struct PackLayout {
+  int32_t free_base, wave_base, waves, nfree;
+};
+__device__ __forceinline__ PackLayout pack_layout_wave(int w, int cnt, bool fill) {
+  const int per = pack_per_wave(w);
+  int32_t nw = pack_waves(cnt, per);
+  const int32_t fl = pack_free_lanes(w, cnt, per, nw);
+  int32_t f = fl;
+  f = wave_incl_scan(f);
+  PackLayout l;
+  l.free_base = f - fl;
+  l.nfree = fill ? __builtin_amdgcn_readlane(f, 63) : 0;
+  if (w == 1) nw = pack_singleton_waves(cnt, l.nfree);
+  int32_t v = nw;
+  v = wave_incl_scan(v);
+  l.wave_base = v - nw;
+  l.waves = v;
+  return l;
+}
+
+// ... kept where every build keeps it: misc (1: waves, 3: free lanes) and,
+// 16 words on, the class tables.
+__device__ __forceinline__ void pack_layout_store(const PackLayout& l, int w, int32_t* misc,
+                                                  int32_t* tables) {
+  tables[2 * kPackTableWords + w] = l.free_base;
+  tables[kPackTableWords + w] = l.wave_base;
+  if (w == kWaveLanes) {
+    misc[1] = l.waves;
+    misc[3] = l.nfree;
+    tables[2 * kPackTableWords + 65] = l.nfree;
+  }
+}
+
+// The env runs this window on the global path.
+__device__ __forceinline__ void build_to_global_path(const Scratch& sc, int e) {
+  sc.fallback[e] = 1;
+  sc.env_waves[e] = 0;
+  sc.big_n[e] = 0;
+  sc.big_np[e] = 0;
+}
+
+__device__ __forceinline__ uint32_t pair_species(const DevState& st, const Scratch& sc, int i,
+                                                 int j) {
+  return sc.multi_species ? (uint32_t)(st.species[i] * kMaxSpecies + st.species[j]) : 0u;
+}
+
+// Pair (i, j) with slots si, sj into its wave's list or, both members of a
+// big cluster, the env's big-pair list (one-workgroup builds; misc 2: a list
+// overflowed -> global path, 6: big pairs; wave_np: the waves' counters).
+__device__ __forceinline__ void emit_pair(const DevState& st, const Scratch& sc, int e, int i,
+                                          int j, int si, int sj, int32_t* misc, int32_t* wave_np) {
+  const uint32_t spp = pair_species(st, sc, i, j);
+  if (si < 0) {
+    const int idx = atomicAdd(&misc[6], 1);
+    if (idx < kBigPairs)
+      sc.big_pairs[(size_t)e * kBigPairs + idx] =
+          big_pair((uint32_t)big_slot(si), (uint32_t)big_slot(sj), spp);
+    else
+      misc[2] = 1;
+    return;
+  }
+  const int wv = slot_wave(si);
+  const int idx = atomicAdd(&wave_np[wv], 1);
+  if (idx < kPairsPerWave)
+    sc.pairs[((size_t)e * sc.wmax + wv) * kPairsPerWave + idx] =
+        wave_pair((uint32_t)slot_lane(si), (uint32_t)slot_lane(sj), spp);
+  else
+    misc[2] = 1;  // a wave with more than kPairsPerWave pairs
+}
+
+// The end of a one-workgroup build: the waves' pair counts, the env's waves
+// (misc 1) or its fallback (misc 2), its big cluster members (5) and pairs (6).
+__device__ __forceinline__ void build_publish(const Scratch& sc, int e, const int32_t* misc,
+                                              const int32_t* wave_np) {
+  const int T = blockDim.x, tid = threadIdx.x;
+  for (int w = tid; w < misc[1]; w += T)
+    sc.wave_npairs[(size_t)e * sc.wmax + w] = min(wave_np[w], kPairsPerWave);
+  if (tid == 0) {
+    sc.env_waves[e] = misc[2] ? 0 : misc[1];
+    sc.fallback[e] = misc[2] ? 1 : 0;
+    sc.big_n[e] = misc[5];
+    sc.big_np[e] = min(misc[6], kBigPairs);
+  }
 }
 
 // Exclusive scan of data[0..n) in LDS by the whole block; data[n] = total.
@@ -1848,22 +1928,6 @@ __device__ __forceinline__ void pair_filter_body(const Derived* __restrict__ d, 
   }
 }
 
-// The packing class v whose free-lane range holds singleton rank r < nfree:
-// the largest v >= 2 with freebase[v] <= r (its range is non-empty).
-// freebase[2..65] is non-decreasing and freebase[65] = nfree > r, so v - 1 =
-// #{u in [2, 65]: freebase[u] <= r}: counted in two rounds of eight
-// independent LDS reads (every 8th entry, then the eight from the last of
-// those <= r) -- two LDS latencies where a binary search waits for six.
-__device__ __forceinline__ int free_class(const int32_t* freebase, int r) {
-  int k8 = -1;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) k8 += freebase[2 + 8 * q] <= r ? 1 : 0;
-  int v = 1 + 8 * k8;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v += freebase[2 + 8 * k8 + q] <= r ? 1 : 0;
-  return v;
-}
-
 // Build step 3, one workgroup per env: union-find over the pair list
 // (connected components = clusters), packing of the clusters into 64-lane
 // wave slots that never straddle a wave, per-wave pair lists.  kBig: the
@@ -1878,11 +1942,9 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
   const size_t base = (size_t)e * N;
   int32_t* wave_sums = reinterpret_cast<int32_t*>(smem);  // 16
   int32_t* misc = wave_sums + 16;                          // 16: 0 flag, 1 waves
-  int32_t* classcnt = misc + 16;                           // 68
-  int32_t* wavebase = classcnt + 68;                       // 68
-  int32_t* freebase = wavebase + 68;                       // 68
+  int32_t* classcnt = misc + 16;                           // the three class tables
   const int wmax = sc.wmax;
-  int32_t* wave_np = freebase + 68;                        // wmax (padded)
+  int32_t* wave_np = classcnt + 3 * kPackTableWords;       // wmax (padded)
   int32_t* parent = wave_np + ((wmax + 3) & ~3);           // N
   const size_t M = (size_t)st.m;
   int32_t* csz = kBig ? sc.gclus + base : parent + N;              // N
@@ -2038,10 +2100,7 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
         if (ok[u]) atomicAdd(&cbase[parent[pr[u] & 0xffffu]], 1);
     }
   __syncthreads();
-  // Lanes reserved per cluster (its packing class w): its size s, or with
-  // one-pass packing max(s, min(pairs, 64, 2 s)), so that the clusters of a
-  // wave have at most 64 pairs (one pair pass per sub-step) unless a cluster
-  // is denser than 2 pairs per particle.  Results do not depend on it.
+  // every root's packing class w and its rank in the class
   for (int i0 = tid; i0 < N; i0 += kU * T) {
     int32_t sz[kU], pc[kU];
 #pragma unroll
@@ -2056,7 +2115,7 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
       const int i = i0 + u * T;
       const bool root = i < N && parent[i] == i;
       const int s = sz[u];
-      const int w = sc.one_pass ? max(s, min(min(pc[u], 64), 2 * s)) : s;
+      const int w = pack_class(s, pc[u], sc.one_pass);
       // one LDS atomic per root (measured, 4096 colloids: the wave-aggregated
       // counters of the packed build cost this one-workgroup build ~0.9 us,
       // cluster build 16.7 -> 15.8 us without them)
@@ -2076,38 +2135,12 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
   // (list overflow) and misc[4] are final here, so every thread decides
   // alike, with no barrier for a flag
   if (misc[0] || misc[4] > min(kBigMax, (int)blockDim.x) || (st.dims == 3 && misc[4] > 0)) {
-    if (tid == 0) {
-      sc.fallback[e] = 1;
-      sc.env_waves[e] = 0;
-      sc.big_n[e] = 0;
-      sc.big_np[e] = 0;
-    }
+    if (tid == 0) build_to_global_path(sc, e);
     return;
   }
-  // Waves per class.  The tail lanes a class leaves free in its waves
-  // (64 - per * w in a full wave, more in its last one) take the singletons
-  // first; only the rest of them get waves of their own (fewer, fuller
-  // waves: the run kernel's cost is per wave).
   if (tid < 64) {
-    const int w = tid + 1;
-    const int per = udiv_small(64, w);
-    const int cnt = classcnt[w];
-    int32_t nw = udiv_small(cnt + per - 1, per);
-    int32_t fl = 0;
-    if (w >= 2 && nw > 0) fl = (nw - 1) * (64 - per * w) + (64 - (cnt - (nw - 1) * per) * w);
-    int32_t f = fl;
-    f = wave_incl_scan(f);
-    freebase[w] = f - fl;
-    const int32_t F = sc.fill_singletons ? __builtin_amdgcn_readlane(f, 63) : 0;
-    if (w == 1) nw = (max(cnt - F, 0) + 63) / 64;
-    int32_t v = nw;
-    v = wave_incl_scan(v);
-    wavebase[w] = v - nw;
-    if (tid == 63) {
-      misc[1] = v;
-      misc[3] = F;
-      freebase[65] = F;
-    }
+    const PackLayout l = pack_layout_wave(tid + 1, classcnt[tid + 1], sc.fill_singletons);
+    pack_layout_store(l, tid + 1, misc, classcnt);
   }
   __syncthreads();
   // Every particle's slot in one pass: its cluster's base (from the root's
@@ -2115,6 +2148,7 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
   // that stores the bases and no barrier before the members read them) plus
   // its rank in the cluster.
   const int nfree = misc[3];
+  const PackTables tabs = pack_tables(classcnt);
   for (int i0 = tid; i0 < N; i0 += kU * T) {
     int32_t rt[kU], ls[kU], sz[kU], rk[kU];
 #pragma unroll
@@ -2135,36 +2169,12 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
       if (i >= N) continue;
       const int root = rt[u], s = sz[u], r = rk[u];
       int slot;
-      if (r == kBigMark) {  // big-cluster member m: slot -1 - m
+      if (r == kBigMark) {
         const int m = atomicAdd(&misc[5], 1);
         sc.big_list[(size_t)e * kBigMax + m] = i;
-        slot = -1 - m;
+        slot = big_slot(m);
       } else {
-        int cb;
-        if (s == 1 && r < nfree) {
-          // the class v whose free-lane range holds r, then wave j and lane
-          const int v = free_class(freebase, r);
-          const int per = udiv_small(64, v);
-          const int nw = udiv_small(classcnt[v] + per - 1, per);
-          const int ffull = 64 - per * v;
-          const int t = r - freebase[v];
-          int j, lane;
-          if (t < (nw - 1) * ffull) {
-            j = udiv_small(t, ffull);
-            lane = per * v + (t - j * ffull);
-          } else {
-            j = nw - 1;
-            lane = (classcnt[v] - (nw - 1) * per) * v + (t - (nw - 1) * ffull);
-          }
-          cb = (wavebase[v] + j) * 64 + lane;
-        } else if (s == 1) {
-          const int r2 = r - nfree;
-          cb = (wavebase[1] + r2 / 64) * 64 + r2 % 64;
-        } else {
-          const int per = udiv_small(64, s), rq = udiv_small(r, per);
-          cb = (wavebase[s] + rq) * 64 + (r - rq * per) * s;
-        }
-        slot = cb + ls[u];
+        slot = pack_base(s, r, tabs, nfree) + ls[u];
         sc.perm[(size_t)e * S + slot] = i;
       }
       lslot[i] = slot;
@@ -2195,37 +2205,12 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
     if (!okp[u]) continue;
     const uint32_t pr = prs[u];
     const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-    const int si = sis[u], sj = sjs[u];
-    const uint32_t spp =
-        sc.multi_species ? (uint32_t)(st.species[i] * kMaxSpecies + st.species[j]) : 0u;
-    if (si < 0) {  // a big cluster's pair (both members of it)
-      const int idx = atomicAdd(&misc[6], 1);
-      if (idx < kBigPairs)
-        sc.big_pairs[(size_t)e * kBigPairs + idx] =
-            (uint32_t)(-1 - si) | ((uint32_t)(-1 - sj) << 10) | (spp << 20);
-      else
-        misc[2] = 1;  // -> global path
-      continue;
-    }
-    const int wv = si >> 6;
-    const int idx = atomicAdd(&wave_np[wv], 1);
-    if (idx < kPairsPerWave)
-      sc.pairs[((size_t)e * wmax + wv) * kPairsPerWave + idx] =
-          (uint32_t)(si & 63) | ((uint32_t)(sj & 63) << 6) | (spp << 12);
-    else
-      misc[2] = 1;  // a wave with more than kPairsPerWave pairs
+    emit_pair(st, sc, e, i, j, sis[u], sjs[u], misc, wave_np);
    }
   }
   __syncthreads();
   SWARM_STAMP(10);
-  for (int w = tid; w < misc[1]; w += T)
-    sc.wave_npairs[(size_t)e * wmax + w] = min(wave_np[w], kPairsPerWave);
-  if (tid == 0) {
-    sc.env_waves[e] = misc[2] ? 0 : misc[1];
-    sc.fallback[e] = misc[2] ? 1 : 0;
-    sc.big_n[e] = misc[5];
-    sc.big_np[e] = min(misc[6], kBigPairs);
-  }
+  build_publish(sc, e, misc, wave_np);
 }
 
 // The large-N build (same result as cluster_build_env<true, false>) with
@@ -2235,8 +2220,8 @@ __device__ __forceinline__ void cluster_build_env(const DevState& st, const Scra
 //   A[i]: union-find parent; then root | rank << 16 (rank = i's lane within
 //         its cluster); then i's wave slot;
 //   B[r]: for a root r, size | pairs << 16 (atomic counters, no carry:
-//         size < 2^16); then class rank | w << 24; then the cluster's first
-//         slot (or kBigMark).
+//         size < 2^16); then its class word; then the cluster's first slot
+//         (or kBigMark).
 // The pair list stays in global memory (read kU at a time).  Used by the
 // large-N builds that union the whole pair list (3-D; 2-D envs with the
 // block-local pair search take the multi-workgroup build, k_mwb_*).
@@ -2246,11 +2231,9 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
   const size_t base = (size_t)e * N;
   int32_t* wave_sums = reinterpret_cast<int32_t*>(smem);  // 16
   int32_t* misc = wave_sums + 16;                          // 16: 0 flag, 1 waves
-  int32_t* classcnt = misc + 16;                           // 68
-  int32_t* wavebase = classcnt + 68;                       // 68
-  int32_t* freebase = wavebase + 68;                       // 68
+  int32_t* classcnt = misc + 16;                           // the three class tables
   const int wmax = sc.wmax;
-  int32_t* wave_np = freebase + 68;                        // wmax (padded)
+  int32_t* wave_np = classcnt + 3 * kPackTableWords;       // wmax (padded)
   int32_t* A = wave_np + ((wmax + 3) & ~3);                // N
   int32_t* B = A + N;                                      // N
   const uint32_t* plist = sc.gplist + (size_t)e * sc.pair_cap;
@@ -2299,12 +2282,12 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
         }
     }
   __syncthreads();
-  // lanes reserved per cluster (cluster_build_env): class w, class rank
+  // every root's packing class w and its rank in the class
   for (int i = tid; i < N; i += T) {
     const bool root = (A[i] & 0xffff) == i;  // roots only
     const uint32_t b = root ? (uint32_t)B[i] : 0u;
     const int s = (int)(b & 0xffffu), pairs = (int)(b >> 16);
-    const int w = sc.one_pass ? max(s, min(min(pairs, 64), 2 * s)) : s;
+    const int w = pack_class(s, pairs, sc.one_pass);
     // the two most frequent classes by one atomic per wave
     const int r1 = wave_class_add(&classcnt[1], root && s <= 64 && w == 1);
     const int r2 = wave_class_add(&classcnt[2], root && s <= 64 && w == 2);
@@ -2313,7 +2296,7 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
       atomicAdd(&misc[4], s);
       B[i] = kBigMark;
     } else {
-      B[i] = (w == 1 ? r1 : (w == 2 ? r2 : atomicAdd(&classcnt[w], 1))) | (w << 24);
+      B[i] = class_word(w == 1 ? r1 : (w == 2 ? r2 : atomicAdd(&classcnt[w], 1)), w);
     }
   }
   __syncthreads();
@@ -2323,66 +2306,21 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
     misc[0] = 1;
   __syncthreads();
   if (misc[0]) {
-    if (tid == 0) {
-      sc.fallback[e] = 1;
-      sc.env_waves[e] = 0;
-      sc.big_n[e] = 0;
-      sc.big_np[e] = 0;
-    }
+    if (tid == 0) build_to_global_path(sc, e);
     return;
   }
-  if (tid < 64) {  // waves per class (cluster_build_env)
-    const int w = tid + 1;
-    const int per = udiv_small(64, w);
-    const int cnt = classcnt[w];
-    int32_t nw = udiv_small(cnt + per - 1, per);
-    int32_t fl = 0;
-    if (w >= 2 && nw > 0) fl = (nw - 1) * (64 - per * w) + (64 - (cnt - (nw - 1) * per) * w);
-    int32_t f = fl;
-    f = wave_incl_scan(f);
-    freebase[w] = f - fl;
-    const int32_t F = sc.fill_singletons ? __builtin_amdgcn_readlane(f, 63) : 0;
-    if (w == 1) nw = (max(cnt - F, 0) + 63) / 64;
-    int32_t v = nw;
-    v = wave_incl_scan(v);
-    wavebase[w] = v - nw;
-    if (tid == 63) {
-      misc[1] = v;
-      misc[3] = F;
-      freebase[65] = F;
-    }
+  if (tid < 64) {
+    const PackLayout l = pack_layout_wave(tid + 1, classcnt[tid + 1], sc.fill_singletons);
+    pack_layout_store(l, tid + 1, misc, classcnt);
   }
   __syncthreads();
   const int nfree = misc[3];
+  const PackTables tabs = pack_tables(classcnt);
   for (int i = tid; i < N; i += T) {
     if ((A[i] & 0xffff) != i) continue;
     const int32_t b = B[i];
     if (b == kBigMark) continue;
-    const int s = (b >> 24) & 0x7f;
-    const int r = b & 0xffffff;
-    int cb;
-    if (s == 1 && r < nfree) {
-      const int v = free_class(freebase, r), per = udiv_small(64, v);
-      const int nw = udiv_small(classcnt[v] + per - 1, per);
-      const int ffull = 64 - per * v;
-      const int t = r - freebase[v];
-      int j, lane;
-      if (t < (nw - 1) * ffull) {
-        j = udiv_small(t, ffull);
-        lane = per * v + (t - j * ffull);
-      } else {
-        j = nw - 1;
-        lane = (classcnt[v] - (nw - 1) * per) * v + (t - (nw - 1) * ffull);
-      }
-      cb = (wavebase[v] + j) * 64 + lane;
-    } else if (s == 1) {
-      const int r2 = r - nfree;
-      cb = (wavebase[1] + r2 / 64) * 64 + r2 % 64;
-    } else {
-      const int per = udiv_small(64, s), rq = udiv_small(r, per);
-      cb = (wavebase[s] + rq) * 64 + (r - rq * per) * s;
-    }
-    B[i] = cb;
+    B[i] = pack_base(class_word_w(b), class_word_rank(b), tabs, nfree);
   }
   __syncthreads();
   for (int i = tid; i < N; i += T) {
@@ -2391,10 +2329,10 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
     const int rank = (int)((uint32_t)a >> 16);
     const int32_t cb = B[root];
     int slot;
-    if (cb == kBigMark) {  // big-cluster member m: slot -1 - m
+    if (cb == kBigMark) {
       const int m = atomicAdd(&misc[5], 1);
       sc.big_list[(size_t)e * kBigMax + m] = i;
-      slot = -1 - m;
+      slot = big_slot(m);
     } else {
       slot = cb + rank;
       sc.perm[(size_t)e * S + slot] = i;
@@ -2414,37 +2352,12 @@ __device__ void cluster_build_env_packed(const DevState& st, const Scratch& sc, 
       if (k0 + u * T >= npairs) continue;
       const uint32_t pr = prs[u];
       const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-      const int si = A[i], sj = A[j];
-      const uint32_t spp =
-        sc.multi_species ? (uint32_t)(st.species[i] * kMaxSpecies + st.species[j]) : 0u;
-      if (si < 0) {  // a big cluster's pair (both members of it)
-        const int idx = atomicAdd(&misc[6], 1);
-        if (idx < kBigPairs)
-          sc.big_pairs[(size_t)e * kBigPairs + idx] =
-              (uint32_t)(-1 - si) | ((uint32_t)(-1 - sj) << 10) | (spp << 20);
-        else
-          misc[2] = 1;  // -> global path
-        continue;
-      }
-      const int wv = si >> 6;
-      const int idx = atomicAdd(&wave_np[wv], 1);
-      if (idx < kPairsPerWave)
-        sc.pairs[((size_t)e * wmax + wv) * kPairsPerWave + idx] =
-            (uint32_t)(si & 63) | ((uint32_t)(sj & 63) << 6) | (spp << 12);
-      else
-        misc[2] = 1;  // a wave with more than kPairsPerWave pairs
+      emit_pair(st, sc, e, i, j, A[i], A[j], misc, wave_np);
     }
   }
   __syncthreads();
   SWARM_STAMP(10);
-  for (int w = tid; w < misc[1]; w += T)
-    sc.wave_npairs[(size_t)e * wmax + w] = min(wave_np[w], kPairsPerWave);
-  if (tid == 0) {
-    sc.env_waves[e] = misc[2] ? 0 : misc[1];
-    sc.fallback[e] = misc[2] ? 1 : 0;
-    sc.big_n[e] = misc[5];
-    sc.big_np[e] = min(misc[6], kBigPairs);
-  }
+  build_publish(sc, e, misc, wave_np);
 }
 
 __global__ __launch_bounds__(1024) void k_cluster_build_packed(DevState st, Scratch sc) {
@@ -2465,8 +2378,8 @@ __global__ __launch_bounds__(1024) void k_cluster_build_packed(DevState st, Scra
 //   gclus[0 .. M):  P, the union-find forest; the pair search writes each
 //                   particle's block-local root (a forest of depth one)
 //   gclus[M .. 2M): B, per root: size | pairs << 16 (k_mwb_size), then
-//                   class rank | class << 24, or kMwbBig | first member
-//                   (k_mwb_class); zeroed by the pair search
+//                   its class word or kMwbBig | first member (k_mwb_class);
+//                   zeroed by the pair search
 //   gclus[2M .. 3M): A, root | rank in the cluster << 16 (k_mwb_size)
 // Every launch boundary orders the phases; inside a launch the workgroups
 // meet only through agent-scope atomics, and the last workgroup of a launch
@@ -2559,7 +2472,7 @@ __global__ __launch_bounds__(256) void k_mwb_size(DevState st, Scratch sc) {
 // workgroup in LDS (wave-aggregated for the singleton and pair classes) and
 // reserved with one global atomic per class and workgroup; a big cluster
 // (wider than a wave) reserves its members' range of the big list.  The
-// last workgroup lays the classes out in waves (cluster_build_env) and
+// last workgroup lays the classes out in waves (pack_layout_wave) and
 // publishes the env's waves and flags, or sends the env to the global path
 // (a list overflowed or too many big-cluster members).
 __global__ __launch_bounds__(1024) void k_mwb_class(DevState st, Scratch sc) {
@@ -2576,7 +2489,7 @@ __global__ __launch_bounds__(1024) void k_mwb_class(DevState st, Scratch sc) {
   const bool root = i < N && (A[i] & 0xffff) == i;
   const uint32_t b = root ? (uint32_t)B[i] : 0u;
   const int s = (int)(b & 0xffffu), pairs = (int)(b >> 16);
-  const int w = sc.one_pass ? max(s, min(min(pairs, 64), 2 * s)) : s;
+  const int w = pack_class(s, pairs, sc.one_pass);
   const int r1 = wave_class_add(lcnt + 1, root && s <= 64 && w == 1);
   const int r2 = wave_class_add(lcnt + 2, root && s <= 64 && w == 2);
   int lr = w == 1 ? r1 : r2;
@@ -2586,9 +2499,9 @@ __global__ __launch_bounds__(1024) void k_mwb_class(DevState st, Scratch sc) {
   __syncthreads();
   if (root) {
     if (s > 64)  // a big cluster, run by k_check's workgroup
-      B[i] = (int32_t)(kMwbBig | (uint32_t)atomicAdd(bm + kBmMisc + 4, s));
+      B[i] = mwb_big_word(atomicAdd(bm + kBmMisc + 4, s));
     else
-      B[i] = (lbase[w] + lr) | (w << 24);
+      B[i] = class_word(lbase[w] + lr, w);
   }
   if (!mwb_last_block(bm + kBmMisc + 8, gridDim.x, &last_flag)) return;
   const int nbig = agent_load(bm + kBmMisc + 4);
@@ -2597,33 +2510,16 @@ __global__ __launch_bounds__(1024) void k_mwb_class(DevState st, Scratch sc) {
   if (over) {
     if (tid == 0) {
       bm[kBmMisc + 0] = 1;
-      sc.fallback[e] = 1;
-      sc.env_waves[e] = 0;
-      sc.big_n[e] = 0;
-      sc.big_np[e] = 0;
+      build_to_global_path(sc, e);
     }
     return;
   }
-  if (tid < 64) {  // waves per class (cluster_build_env)
-    const int w = tid + 1;
-    const int per = udiv_small(64, w);
-    const int cnt = agent_load(bm + kBmClass + w);
-    int32_t nw = udiv_small(cnt + per - 1, per);
-    int32_t fl = 0;
-    if (w >= 2 && nw > 0) fl = (nw - 1) * (64 - per * w) + (64 - (cnt - (nw - 1) * per) * w);
-    int32_t f = fl;
-    f = wave_incl_scan(f);
-    bm[kBmFree + w] = f - fl;
-    const int32_t F = sc.fill_singletons ? __builtin_amdgcn_readlane(f, 63) : 0;
-    if (w == 1) nw = (max(cnt - F, 0) + 63) / 64;
-    int32_t v = nw;
-    v = wave_incl_scan(v);
-    bm[kBmWave + w] = v - nw;
+  if (tid < 64) {
+    const PackLayout l =
+        pack_layout_wave(tid + 1, agent_load(bm + kBmClass + tid + 1), sc.fill_singletons);
+    pack_layout_store(l, tid + 1, bm + kBmMisc, bm + kBmClass);
     if (tid == 63) {
-      bm[kBmMisc + 1] = v;
-      bm[kBmMisc + 3] = F;
-      bm[kBmFree + 65] = F;
-      sc.env_waves[e] = v;
+      sc.env_waves[e] = l.waves;
       sc.fallback[e] = 0;  // set by k_mwb_pairs when a list overflows
       sc.big_n[e] = nbig;
       sc.big_np[e] = 0;
@@ -2631,51 +2527,26 @@ __global__ __launch_bounds__(1024) void k_mwb_class(DevState st, Scratch sc) {
   }
 }
 
-// A particle's wave slot from its root's class word and the class layout
-// (tables in LDS: counts, first waves, free-lane bases; misc[3] = free lanes).
-__device__ __forceinline__ int mwb_slot(int32_t a, int32_t broot, const int32_t* cls,
-                                        const int32_t* wbase, const int32_t* fbase, int nfree) {
+// A particle's wave slot from its root's class word and the class layout.
+__device__ __forceinline__ int mwb_slot(int32_t a, int32_t broot, const PackTables& tabs,
+                                        int nfree) {
   const int rank = (int)((uint32_t)a >> 16);
-  if ((uint32_t)broot & kMwbBig) return -1 - (int)(((uint32_t)broot & ~kMwbBig) + rank);
-  const int s = (broot >> 24) & 0x7f;
-  const int r = broot & 0xffffff;
-  int cb;
-  if (s == 1 && r < nfree) {
-    const int v = free_class(fbase, r), per = udiv_small(64, v);
-    const int nw = udiv_small(cls[v] + per - 1, per);
-    const int ffull = 64 - per * v;
-    const int t = r - fbase[v];
-    int j, lane;
-    if (t < (nw - 1) * ffull) {
-      j = udiv_small(t, ffull);
-      lane = per * v + (t - j * ffull);
-    } else {
-      j = nw - 1;
-      lane = (cls[v] - (nw - 1) * per) * v + (t - (nw - 1) * ffull);
-    }
-    cb = (wbase[v] + j) * 64 + lane;
-  } else if (s == 1) {
-    const int r2 = r - nfree;
-    cb = (wbase[1] + r2 / 64) * 64 + r2 % 64;
-  } else {
-    const int per = udiv_small(64, s), rq = udiv_small(r, per);
-    cb = (wbase[s] + rq) * 64 + (r - rq * per) * s;
-  }
-  return cb + rank;
+  if (mwb_is_big(broot)) return big_slot(mwb_big_first(broot) + rank);
+  return pack_base(class_word_w(broot), class_word_rank(broot), tabs, nfree) + rank;
 }
 
 // k_mwb_slots: every particle's wave slot (perm, slot_of, root); a
 // big-cluster member lists its pairs (as the lower index) for k_check's
 // big-cluster run, its partner's member index worked out the same way.
 __global__ __launch_bounds__(256) void k_mwb_slots(DevState st, Scratch sc) {
-  __shared__ int32_t tab[3 * 68];
+  __shared__ int32_t tab[3 * kPackTableWords];
   const int e = blockIdx.y, N = st.n, tid = threadIdx.x;
   const size_t M = (size_t)st.m, base = (size_t)e * N;
   const int32_t* bm = sc.bmisc + (size_t)e * kBmWords;
   if (bm[kBmMisc + 0]) return;  // the env runs on the global path (k_mwb_class)
-  for (int k = tid; k < 3 * 68; k += blockDim.x) tab[k] = bm[kBmClass + k];
+  for (int k = tid; k < 3 * kPackTableWords; k += blockDim.x) tab[k] = bm[kBmClass + k];
   __syncthreads();
-  const int32_t *cls = tab, *wbase = tab + 68, *fbase = tab + 136;
+  const PackTables tabs = pack_tables(tab);
   const int nfree = bm[kBmMisc + 3];
   const int32_t* B = sc.gclus + M + base;
   const int32_t* A = sc.gclus + 2 * M + base;
@@ -2683,14 +2554,14 @@ __global__ __launch_bounds__(256) void k_mwb_slots(DevState st, Scratch sc) {
   if (i >= N) return;
   const int32_t a = A[i];
   const int root = a & 0xffff;
-  const int slot = mwb_slot(a, B[root], cls, wbase, fbase, nfree);
+  const int slot = mwb_slot(a, B[root], tabs, nfree);
   sc.slot_of[base + i] = slot;
   sc.root[base + i] = root;
   if (slot >= 0) {
     sc.perm[(size_t)e * sc.S + slot] = i;
     return;
   }
-  sc.big_list[(size_t)e * kBigMax + (-1 - slot)] = i;
+  sc.big_list[(size_t)e * kBigMax + big_slot(slot)] = i;
   // the member's pairs (i the lower index): contiguous in the pair list
   const int n_i = (int)((uint32_t)sc.lroot[base + i] >> 16);
   const int off = sc.gclus[3 * M + base + i];
@@ -2698,13 +2569,11 @@ __global__ __launch_bounds__(256) void k_mwb_slots(DevState st, Scratch sc) {
   for (int k = 0; k < n_i && off + k < sc.pair_cap; ++k) {
     const int j = (int)(plist[off + k] >> 16);
     const int32_t aj = A[j];
-    const int sj = mwb_slot(aj, B[aj & 0xffff], cls, wbase, fbase, nfree);
-    const uint32_t spp =
-        sc.multi_species ? (uint32_t)(st.species[i] * kMaxSpecies + st.species[j]) : 0u;
+    const int sj = mwb_slot(aj, B[aj & 0xffff], tabs, nfree);
     const int idx = atomicAdd(&sc.big_np[e], 1);
     if (idx < kBigPairs)
       sc.big_pairs[(size_t)e * kBigPairs + idx] =
-          (uint32_t)(-1 - slot) | ((uint32_t)(-1 - sj) << 10) | (spp << 20);
+          big_pair((uint32_t)big_slot(slot), (uint32_t)big_slot(sj), pair_species(st, sc, i, j));
     else
       sc.fallback[e] = 1;  // -> global path
   }
@@ -2739,9 +2608,7 @@ __global__ __launch_bounds__(256) void k_mwb_pairs(DevState st, Scratch sc) {
   for (int k = 0; k < n_i; ++k) {
     const int j = (int)(plist[off + k] >> 16);
     const int sj = sc.slot_of[base + j];
-    const uint32_t spp =
-        sc.multi_species ? (uint32_t)(st.species[i] * kMaxSpecies + st.species[j]) : 0u;
-    out[k] = (uint32_t)lane | ((uint32_t)(sj & 63) << 6) | (spp << 12);
+    out[k] = wave_pair((uint32_t)lane, (uint32_t)slot_lane(sj), pair_species(st, sc, i, j));
   }
 }
 
@@ -3216,12 +3083,12 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
   // the first pass's pair stays in a register; a wave with more passes
   // (rare: a cluster denser than 2 pairs per particle) reloads the others
   // from L2 each sub-step, so they do not hold registers for the run
-  const uint32_t pr0 = lane < np ? pw[lane] : 0xffffffffu;
+  const uint32_t pr0 = lane < np ? pw[lane] : kPairEmpty;
   // two passes (a cluster with more than 64 pairs: 65-128 in the wave): the
   // second pass's pair in a register too, and both passes unrolled so their
   // LDS reads and force arithmetic interleave (C5: such a wave set the
   // launch's duration in a third of the windows, 1.7x a one-pass wave)
-  const uint32_t pr1 = npass == 2 && 64 + lane < np ? pw[64 + lane] : 0xffffffffu;
+  const uint32_t pr1 = npass == 2 && 64 + lane < np ? pw[64 + lane] : kPairEmpty;
   lacc_x[lane] = 0ull;
   lacc_y[lane] = 0ull;
   const uint32_t k0 = d->key0, k1 = d->key1 ^ (uint32_t)e;
@@ -3361,9 +3228,9 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
           const uint32_t e_ = q == 0 ? pr0
                                      : (kPass == 2 ? pr1
                                                    : (q * 64 + lane < np ? pw[q * 64 + lane]
-                                                                         : 0xffffffffu));
-          const int a = e_ == 0xffffffffu ? lane : (int)(e_ & 63u);
-          const int b = e_ == 0xffffffffu ? lane : (int)((e_ >> 6) & 63u);
+                                                                         : kPairEmpty));
+          const int a = e_ == kPairEmpty ? lane : wave_pair_a(e_);
+          const int b = e_ == kPairEmpty ? lane : wave_pair_b(e_);
           // both ends' positions straight from their lanes' registers
           // (ds_bpermute: no LDS row written and waited for first; same-box
           // A/B: E = 1 run 50.9 -> 50.3 us, E = 64 247.7 -> 244.5 us)
@@ -3392,7 +3259,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
             // after them (spec_fix below), so the sums are the same integers
             const int qq = q & 1;  // (kSpec: q < 2, unrolled)
             if (kMulti) {
-              const int sp = (int)((e_ >> 12) & 255u);
+              const int sp = wave_pair_spp(e_);
               pair_vals(pt.cut2[sp], pt.sig6[sp], eps24, rx, ry, sv_x[qq], sv_y[qq]);
             } else {
               pair_vals(cut2_0, sig6_0, eps24, rx, ry, sv_x[qq], sv_y[qq]);
@@ -3404,7 +3271,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
             sa[qq] = a;
             sb[qq] = b;
           } else if (kMulti) {
-            const int sp = (int)((e_ >> 12) & 255u);
+            const int sp = wave_pair_spp(e_);
             pair_fix_sel(pt.cut2[sp], pt.sig6[sp], eps24, rx, ry, fx, fy);
           } else {
             pair_fix_sel(cut2_0, sig6_0, eps24, rx, ry, fx, fy);
@@ -3887,8 +3754,8 @@ __device__ void run_big_clusters(const Derived* __restrict__ d, const DevState& 
     for (int u = 0; u < kPer; ++u) {
       // (wave-uniform: a wave whose slots all lie past the list skips them)
       if (u * T + (tid & ~63) >= np) break;
-      const int a = (int)(pr[u] & 1023u), b = (int)((pr[u] >> 10) & 1023u);
-      const int sp = (int)(pr[u] >> 20);
+      const int a = big_pair_a(pr[u]), b = big_pair_b(pr[u]);
+      const int sp = big_pair_spp(pr[u]);
       const uint2 pa = lp[a], pb = lp[b];
       const float rx = (float)(int32_t)(pb.x - pa.x) * sx0;
       const float ry = (float)(int32_t)(pb.y - pa.y) * sx1;
@@ -4311,7 +4178,7 @@ __device__ __forceinline__ void check_body(const Derived* __restrict__ d, const 
         c.root = nlist ? 0 : sc.root[base + m];
         c.np = 0;
         if (!nlist && c.sm >= 0) {
-          const size_t wl = (size_t)e * sc.wmax + (c.sm >> 6);
+          const size_t wl = (size_t)e * sc.wmax + slot_wave(c.sm);
           const uint4* pw = reinterpret_cast<const uint4*>(sc.pairs + wl * kPairsPerWave);
           c.np = sc.wave_npairs[wl];
 #pragma unroll
@@ -4351,27 +4218,27 @@ __device__ __forceinline__ void check_body(const Derived* __restrict__ d, const 
               for (int u = 0; u < 8; ++u) listed |= (v[u] & 0xffffff) == j;
             }
           } else if (rj == c.root && sm < 0) {  // same big cluster
-            const uint32_t bm = (uint32_t)(-1 - sm), bj = (uint32_t)(-1 - sj);
-            const uint32_t k1 = bm | bj << 10, k2 = bj | bm << 10;
+            const uint32_t bm = (uint32_t)big_slot(sm), bj = (uint32_t)big_slot(sj);
+            const uint32_t k1 = big_pair_members(bm, bj), k2 = big_pair_members(bj, bm);
             const uint4* bp = reinterpret_cast<const uint4*>(sc.big_pairs + (size_t)e * kBigPairs);
             const int np = min(sc.big_np[e], kBigPairs);
-            listed = list_holds(bp, np, 0xfffffu, k1, k2);
+            listed = list_holds(bp, np, kBigPairMembers, k1, k2);
           } else if (rj == c.root) {  // same wave: its pairs
-            const uint32_t lm = (uint32_t)(sm & 63), lj = (uint32_t)(sj & 63);
-            const uint32_t k1 = lm | lj << 6, k2 = lj | lm << 6;
+            const uint32_t lm = (uint32_t)slot_lane(sm), lj = (uint32_t)slot_lane(sj);
+            const uint32_t k1 = wave_pair_lanes(lm, lj), k2 = wave_pair_lanes(lj, lm);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               const uint32_t w[4] = {c.l[u].x, c.l[u].y, c.l[u].z, c.l[u].w};
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const uint32_t x = w[q] & 0xfffu;
+                const uint32_t x = w[q] & kWavePairLanes;
                 listed |= 4 * u + q < c.np && (x == k1 || x == k2);
               }
             }
             if (!listed && c.np > 16) {
               const uint4* pw = reinterpret_cast<const uint4*>(
-                  sc.pairs + ((size_t)e * sc.wmax + (sm >> 6)) * kPairsPerWave);
-              listed = list_holds(pw + 4, c.np - 16, 0xfffu, k1, k2);
+                  sc.pairs + ((size_t)e * sc.wmax + slot_wave(sm)) * kPairsPerWave);
+              listed = list_holds(pw + 4, c.np - 16, kWavePairLanes, k1, k2);
             }
           }
           if (!listed) misc[1] = 1;

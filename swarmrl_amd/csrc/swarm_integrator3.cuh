@@ -714,7 +714,7 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
   const int np = sc.wave_npairs[(size_t)e * sc.wmax + w];
   const int npass = (np + 63) >> 6;
   const uint32_t* pw = sc.pairs + ((size_t)e * sc.wmax + w) * kPairsPerWave;
-  const uint32_t pr0 = lane < np ? pw[lane] : 0xffffffffu;
+  const uint32_t pr0 = lane < np ? pw[lane] : kPairEmpty;
   lacc_x[lane] = 0ull;
   lacc_y[lane] = 0ull;
   lacc_z[lane] = 0ull;
@@ -752,16 +752,16 @@ __device__ __forceinline__ void run_wave3(const Derived* __restrict__ d, const D
       wave_lds_sync();
       for (int ps = 0; ps < (kPass == 1 ? 1 : npass); ++ps) {
         const uint32_t e_ =
-            ps == 0 ? pr0 : (ps * 64 + lane < np ? pw[ps * 64 + lane] : 0xffffffffu);
-        const int a = e_ == 0xffffffffu ? lane : (int)(e_ & 63u);
-        const int b = e_ == 0xffffffffu ? lane : (int)((e_ >> 6) & 63u);
+            ps == 0 ? pr0 : (ps * 64 + lane < np ? pw[ps * 64 + lane] : kPairEmpty);
+        const int a = e_ == kPairEmpty ? lane : wave_pair_a(e_);
+        const int b = e_ == kPairEmpty ? lane : wave_pair_b(e_);
         const uint4 pa = lpos_w[a], pb = lpos_w[b];
         const float rx = (float)(int32_t)(pb.x - pa.x) * sx[0];
         const float ry = (float)(int32_t)(pb.y - pa.y) * sx[1];
         const float rz = (float)(int32_t)(pb.z - pa.z) * sx[2];
         int64_t fx, fy, fz;  // on a; b receives exactly the negation
         if (kMulti) {
-          const int sp = (int)((e_ >> 12) & 255u);
+          const int sp = wave_pair_spp(e_);
           pair_fix_sel3(pt.cut2[sp], pt.sig6[sp], eps24, rx, ry, rz, fx, fy, fz);
         } else {
           pair_fix_sel3(cut2_0, sig6_0, eps24, rx, ry, rz, fx, fy, fz);
@@ -918,12 +918,12 @@ __global__ __launch_bounds__(1024) void k_check3(const Derived* __restrict__ d, 
               listed |= (sc.nl[(size_t)k * M + base + m] & 0xffffff) == j;
           } else if (sc.root[base + j] == sc.root[base + m]) {  // same wave: its pairs
             const int sm = sc.slot_of[base + m], sj = sc.slot_of[base + j];
-            const int wv = sm >> 6;
-            const uint32_t lm = (uint32_t)(sm & 63), lj = (uint32_t)(sj & 63);
+            const int wv = slot_wave(sm);
+            const uint32_t lm = (uint32_t)slot_lane(sm), lj = (uint32_t)slot_lane(sj);
             const uint32_t* pw = sc.pairs + ((size_t)e * sc.wmax + wv) * kPairsPerWave;
             const int np = sc.wave_npairs[(size_t)e * sc.wmax + wv];
             for (int k = 0; k < np; ++k) {
-              const uint32_t a = pw[k] & 63u, b = (pw[k] >> 6) & 63u;
+              const uint32_t a = (uint32_t)wave_pair_a(pw[k]), b = (uint32_t)wave_pair_b(pw[k]);
               listed |= (a == lm && b == lj) || (a == lj && b == lm);
             }
           }

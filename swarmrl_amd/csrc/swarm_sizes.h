@@ -2,7 +2,9 @@
 // host's planning (swarm_plan.h), the launch layer (swarm_engine_host.cuh) and
 // the kernels' own layouts share.  Plain C++17, no HIP types: a host compiler
 // reads it alone (tests/csrc/plan_selftest.cpp), the device headers include it
-// and use the names in namespace swarm as before.
+// and use the names in namespace swarm as before.  (The host-readable headers:
+// this one, swarm_plan.h, swarm_select.h and swarm_pack.h, the packing
+// contract between the cluster build and the run kernels.)
 #pragma once
 
 #include <stddef.h>

@@ -444,6 +444,54 @@ def test_large_build_plain_pair_search_bit_exact(k, monkeypatch):
         assert fb[0] == 0 and waves[0] > 0, (w, fb, waves)
 
 
+@pytest.mark.parametrize("k", [92, 145])
+def test_large_builds_agree_on_waves(k, monkeypatch):
+    """The packing rule is one rule (swarm_pack.h): the one-workgroup large-N
+    build (SWARMRL_AMD_LOCAL_UF=0: k_cluster_build_packed at 8464 colloids,
+    k_cluster_build<true, false> at 21 025) and the multi-workgroup build
+    (the default, k_mwb_*) pack the same state into the same number of waves
+    -- the wave count is a function of the class counts alone -- and both
+    integrate it bit-exactly without fallback.  The jittered lattice of
+    test_large_build_plain_pair_search_bit_exact: spacing 5 with +-1 of jitter
+    against a link length of 4, so about one lattice bond in eight links its
+    ends and the state holds dimers, trimers and longer chains; more waves
+    than ceil(n / 64) shows that it is not all singletons."""
+    from gpu_harness import Harness, species_list
+
+    monkeypatch.setenv("SWARMRL_AMD_NLIST", "0")
+    rng = np.random.default_rng(90 + k)
+    n, a = k * k, 5.0
+    box = [k * a, k * a, k * a]
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 2)
+    pos = np.zeros((n, 3))
+    pos[:, :2] = (g + 0.5) * a + rng.uniform(-1.0, 1.0, (n, 2))
+    th = 2 * np.pi * rng.random(n)
+    st0 = oracle.state_from_positions(pos, np.stack([np.cos(th), np.sin(th), np.zeros(n)], 1), box)
+    acts = [(rng.choice([0.0, 10.0], n).astype(np.float32),
+             rng.choice([-10.0, 0.0, 10.0], n).astype(np.float32)) for _ in range(2)]
+    refs, waves_of = [], {}
+    for local_uf in ("0", None):
+        if local_uf is None:
+            monkeypatch.delenv("SWARMRL_AMD_LOCAL_UF", raising=False)
+        else:
+            monkeypatch.setenv("SWARMRL_AMD_LOCAL_UF", local_uf)
+        h = Harness(box, 1e-3, 1.0239, 1.0239, 3, species_list()[:1], np.zeros(n, int))
+        h.upload([st0])
+        for w, (f, t) in enumerate(acts):
+            h.set_actions(f, t)
+            h.integrate(5)
+            if len(refs) == w:  # the oracle's windows, computed once for both builds
+                prev = refs[-1] if refs else st0
+                refs.append(oracle.bd_run(h.op, prev, np.zeros(n), f, t, 5, step0=5 * w)[0])
+            _eq(h.download()[0], refs[w])
+            fb, waves = h.window_stats()
+            print(f"k={k} LOCAL_UF={local_uf} window {w}: fallback {fb[0]} waves {waves[0]}")
+            assert fb[0] == 0 and waves[0] > -(-n // 64), (local_uf, w, fb, waves)
+            waves_of.setdefault(w, []).append(int(waves[0]))
+    for w, (one_wg, mwb) in waves_of.items():
+        assert one_wg == mwb, (w, one_wg, mwb)
+
+
 @pytest.mark.parametrize("E,n,box_len,env", [
     (1, 2000, 90.0, {}),                                   # 16 lanes per agent
     (20, 4096, 200.0, {"SWARMRL_AMD_VISION_G": "4"}),
