@@ -103,6 +103,10 @@ void derive(const swarm_params_t& p, Derived& d) {
     }
   d.skin = (float)kSkinUm;
   d.rc_max_f = (float)d.rc_max;
+  {
+    const double g = 0.99 * 0.25 * std::min(p.box[0], p.box[1]);
+    d.glim2 = (float)(g * g);
+  }
   d.eps24 = (float)(24.0 * p.wca_epsilon);
   d.n_species = p.n_species;
   d.key0 = (uint32_t)p.seed;

@@ -51,6 +51,25 @@
 #ifndef SWARM_HELPER_WIN2
 #define SWARM_HELPER_WIN2 0
 #endif
+// Round 15, the latency schedule's sub-step (kSched != 0) trimmed; each 0
+// restores the round-14 instruction sequence for a same-box A/B:
+// the image counters carried once per window, not per sub-step (window_carry)
+#ifndef SWARM_RUN_WIN_CARRY
+#define SWARM_RUN_WIN_CARRY 1
+#endif
+// the pair's second end through ds_sub_u64, as in the throughput kernel
+#ifndef SWARM_RUN_SUB64
+#define SWARM_RUN_SUB64 1
+#endif
+// helper mode: no read of the helper's count once it has published the
+// whole window
+#ifndef SWARM_RUN_HELP_DONE
+#define SWARM_RUN_HELP_DONE 1
+#endif
+// the next normals through a running pointer, not from s + 1 each sub-step
+#ifndef SWARM_RUN_NOISE_PTR
+#define SWARM_RUN_NOISE_PTR 1
+#endif
 
 namespace swarm {
 
@@ -93,6 +112,10 @@ struct Derived {
   float eps24;
   float skin;
   float rc_max_f;
+  // (0.99 / 4 of the shorter of the box's x and y sides)^2: a particle whose
+  // displacement from the window start stays below it on every sub-step
+  // keeps the once-per-window image carry exact (window_carry)
+  float glim2;
   int32_t n_species;
   uint32_t key0, key1;
   int32_t noisy;
@@ -811,18 +834,47 @@ __device__ __forceinline__ void apply_carry(PState& p, const Carry& c) {
   p.ix += (int32_t)(((int64_t)(uint64_t)c.qx0 + (int64_t)c.dqx) >> 32);
   p.iy += (int32_t)(((int64_t)(uint64_t)c.qy0 + (int64_t)c.dqy) >> 32);
 }
+// The image carries of a whole window at once (no_img sub-steps: q alone is
+// advanced, the images are read only after the window).  With q0 the window
+// start and d = (int32_t)(q_end - q0), the images move by
+// floor((q0 + d) / 2^32).  Exact when |(int32_t)(q_s - q0)| < 2^30 on both
+// axes after every sub-step s: each dq_s (an int32) is then the difference of
+// two such values, so sum dq_s = d as integers, and the per-step carries
+// floor((q_{s-1} + dq_s) / 2^32) telescope to floor((q0 + d) / 2^32).  (One
+// sub-step cannot slip past the test by wrapping: from |d_{s-1}| < 2^30 and
+// |dq_s| <= 2^31 the true d_s lies within +-3 2^30, where the wrapped value
+// is below 2^30 only if the true one is.)
+// Returns whether the window's largest squared displacement dmax2 (the max
+// over its sub-steps of ddx^2 + ddy^2, dd = (float)(int32_t)(q_s - q0) sx)
+// proves that: dmax2 < Derived::glim2 = (0.99 L / 4)^2, L the shorter side.
+// A coordinate off by 2^30 units or more gives dd >= 2^30 sx exactly
+// (int -> float and the product round monotonically, 2^30 sx is exact), and
+// sx >= (L / 2^32)(1 - 2^-24), so dd^2 >= (L / 4)^2 (1 - 2^-22) > glim2.
+// false: the images are not to be used (the window is re-run with per-step
+// carries, window_tail).
+__device__ __forceinline__ bool window_carry(PState& p, uint32_t q0x, uint32_t q0y, float dmax2,
+                                             float glim2) {
+  const int32_t dx = (int32_t)(p.qx - q0x), dy = (int32_t)(p.qy - q0y);
+  p.ix += (int32_t)(((int64_t)(uint64_t)q0x + (int64_t)dx) >> 32);
+  p.iy += (int32_t)(((int64_t)(uint64_t)q0y + (int64_t)dy) >> 32);
+  return dmax2 < glim2;
+}
 __device__ __forceinline__ void bd_translate_f(const PConst& c, PState& p, float fx, float fy,
                                                float fs, float tz, float fex, float fey,
                                                uint32_t k0, uint32_t k1, uint32_t id,
                                                uint64_t step, bool last, float* vx, float* vy,
                                                float* w, const float* g, float sn, float cs,
-                                               Carry* carry = nullptr, bool adc = false) {
+                                               Carry* carry = nullptr, bool adc = false,
+                                               bool no_img = false) {
   const float F[2] = {fx, fy};
   int32_t dqx, dqy;
   // (without noise sigx = sigy = 0: g is finite, so sig g = +-0 changes no
   // displacement)
   bd_dq(c, F[0], F[1], fs, fex, fey, sn, cs, g, &fx, &fy, &dqx, &dqy);
-  if (carry) {
+  if (no_img) {  // (a compile-time constant at every call; window_carry)
+    p.qx += (uint32_t)dqx;
+    p.qy += (uint32_t)dqy;
+  } else if (carry) {
     *carry = Carry{p.qx, p.qy, dqx, dqy};
     p.qx += (uint32_t)dqx;
     p.qy += (uint32_t)dqy;
@@ -886,12 +938,16 @@ __device__ __forceinline__ bool sd_step(const PConst& c, PState& p, int64_t ax, 
 // End of a cluster or neighbour-list window for particle i of env e (gi):
 // its largest displacement since the window start, and with half the skin
 // or more a place on the mover list (the exact test of k_check / k_check3).
+// redo (window_carry said no): the env's mover count is pushed past
+// kMaxMovers, which the check answers with the exact re-run from the window's
+// snapshot on the global path (per-step carries) -- no word of its own, and
+// nothing new for the check to read.
 __device__ __forceinline__ void window_tail(const Derived* d, const Scratch& sc, int e, int i,
-                                            size_t gi, float dmax2) {
+                                            size_t gi, float dmax2, bool redo = false) {
   const float disp = sqrt_rn(dmax2);
   sc.disp[gi] = disp;
-  if (!(disp < 0.5f * d->skin)) {
-    const int k = atomicAdd(&sc.nmov[e], 1);
+  if (redo || !(disp < 0.5f * d->skin)) {
+    const int k = atomicAdd(&sc.nmov[e], redo ? kMaxMovers + 1 : 1);
     if (k < kMaxMovers) sc.movers[(size_t)e * kMaxMovers + k] = i;
   }
 }
@@ -3111,6 +3167,9 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
   float vx = 0.0f, vy = 0.0f, om = 0.0f;
   const size_t tstep = noise_step_stride(M), ts = noise_comp_stride(M);
   const float* tcol = kTable ? table + noise_index(M, gi, 0, 0) : nullptr;
+  // (kNoisePtr: the next sub-step's normals, a pointer advanced per sub-step)
+  constexpr bool kNoisePtr = SWARM_RUN_NOISE_PTR && kSched != 0;
+  const float* tnext = kTable ? tcol + tstep : nullptr;
   float gn[3] = {0.0f, 0.0f, 0.0f};
   StepNoise noise;  // !kTable: the window's normals drawn here, group by group
   noise.tab = ntab;
@@ -3138,15 +3197,23 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
   };
   float dir[2];
   sincos_turn(an0, &dir[0], &dir[1]);
-  auto substep = [&](const int s, auto last_t, auto pass_t) __attribute__((always_inline)) {
+  // helper mode: the helper's count as the last polling sub-step read it;
+  // once it is kHelpDone every director of the window is in LDS, and the
+  // sub-steps after it (kPoll = false) neither read the count nor branch on it
+  int hseen = 0;
+  bool redo = false;  // window_carry: the window's images are not exact
+  auto substep = [&](const int s, auto last_t, auto pass_t, auto poll_t)
+                     __attribute__((always_inline)) {
     constexpr bool kLast = decltype(last_t)::value;
     constexpr int kPass = decltype(pass_t)::value;  // 0, 1, 2 or 4: up to npass
+    constexpr bool kPoll = decltype(poll_t)::value;
 #ifdef SWARM_PHASE_TIMING
     if (stamp) t0s = t1s = __builtin_amdgcn_s_memtime();
 #endif
     float gt[3] = {gn[0], gn[1], gn[2]};
     if (kTable && !kLast) {  // the next sub-step's normals, one sub-step ahead
-      const float* nx = tcol + (size_t)(s + 1) * tstep;
+      const float* nx = kNoisePtr ? tnext : tcol + (size_t)(s + 1) * tstep;
+      if (kNoisePtr) tnext += tstep;
       gn[0] = nx[0];
       gn[1] = nx[ts];
       gn[2] = nx[2 * ts];
@@ -3200,8 +3267,10 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     auto director = [&]() __attribute__((always_inline)) {
       if constexpr (kHelper) {
         if (!kLast) {  // the count first, then the director (LDS order)
-          hprog = __hip_atomic_load(hl.prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          if (kPoll) {
+            hprog = __hip_atomic_load(hl.prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          }
           const float2 dv = hl.dir[(size_t)(s + 1) * 64 + lane];
           dnext[0] = dv.x;
           dnext[1] = dv.y;
@@ -3219,6 +3288,8 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     constexpr bool kSpec = kSched >= 3 && (kPass == 1 || kPass == 2);
     // speculative read-back conversion, image carries deferred (any pass count)
     constexpr bool kDefer = kSched >= 3 && kPass > 0 && !kWalls;
+    // ... or not at all: one carry after the window (window_carry)
+    constexpr bool kWinCarry = kDefer && SWARM_RUN_WIN_CARRY;
     float sv_x[2] = {0.0f, 0.0f}, sv_y[2] = {0.0f, 0.0f};
     int sa[2] = {lane, lane}, sb[2] = {lane, lane};
     bool spec_ok = true;
@@ -3244,10 +3315,13 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
             rotate();
             if (!kHelper || !SWARM_HELPER_WIN2) {  // (helper: the round trip's window)
               prev_disp();
-              if (kDefer) apply_carry(p, carry);
+              if (kDefer && !kWinCarry) apply_carry(p, carry);
             }
             // pinned here (the compiler would sink them behind the vote branch)
-            __asm__ volatile("" : "+v"(an_next), "+v"(dmax2), "+v"(p.ix), "+v"(p.iy));
+            if (kWinCarry)
+              __asm__ volatile("" : "+v"(an_next), "+v"(dmax2));
+            else
+              __asm__ volatile("" : "+v"(an_next), "+v"(dmax2), "+v"(p.ix), "+v"(p.iy));
             __builtin_amdgcn_sched_barrier(0);
           }
           const float rx = (float)(int32_t)(pb.x - pa.x) * sx0;
@@ -3282,7 +3356,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
           // itself (lds_sub_u64); atomicSub compiles to ds_add_u64 of the
           // negated value, a 64-bit negation (two VALU operations and a
           // hazard wait) per component and pass
-          if (kSched == 0) {
+          if (kSched == 0 || SWARM_RUN_SUB64) {
             lds_sub_u64_xy(&lacc_x[b], (unsigned long long)fx, (unsigned long long)fy);
           } else {
             atomicSub(&lacc_x[b], (unsigned long long)fx);
@@ -3313,8 +3387,12 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
           const int64_t ry_ = wide(sv_y[qq]) - (int64_t)__float2int_rn(sv_y[qq]);
           atomicAdd(&lacc_x[sa[qq]], (unsigned long long)rx_);
           atomicAdd(&lacc_y[sa[qq]], (unsigned long long)ry_);
-          atomicSub(&lacc_x[sb[qq]], (unsigned long long)rx_);
-          atomicSub(&lacc_y[sb[qq]], (unsigned long long)ry_);
+          if (SWARM_RUN_SUB64) {
+            lds_sub_u64_xy(&lacc_x[sb[qq]], (unsigned long long)rx_, (unsigned long long)ry_);
+          } else {
+            atomicSub(&lacc_x[sb[qq]], (unsigned long long)rx_);
+            atomicSub(&lacc_y[sb[qq]], (unsigned long long)ry_);
+          }
         }
         wave_lds_sync();
         ax += (int64_t)lacc_x[lane];
@@ -3329,8 +3407,11 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
         // the round trip's latency window holds no rotation in helper mode:
         // the previous sub-step's displacement and image carries go here
         prev_disp();
-        if (kDefer) apply_carry(p, carry);
-        __asm__ volatile("" : "+v"(dmax2), "+v"(p.ix), "+v"(p.iy));
+        if (kDefer && !kWinCarry) apply_carry(p, carry);
+        if (kWinCarry)
+          __asm__ volatile("" : "+v"(dmax2));
+        else
+          __asm__ volatile("" : "+v"(dmax2), "+v"(p.ix), "+v"(p.iy));
       }
       __builtin_amdgcn_sched_barrier(0);
     } else {
@@ -3372,13 +3453,13 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       // speculative read-back conversion: the translation runs from the
       // int32 view of the sums while the wave vote resolves; the rare wave
       // with a sum beyond int32 redoes it from the exact conversion
-      // the image carries are applied in the next sub-step's exchange window
-      // (the last sub-step applies its own)
+      // the image carries: once after the window (kWinCarry), else applied
+      // in the next sub-step's exchange window (the last sub-step its own)
       const PState p0 = p;
       const bool fits = wave_all2(fits_i32(ax), fits_i32(ay));
       bd_translate_f(pc, p, (float)(int32_t)ax, (float)(int32_t)ay, fs, tz, fxe, fye, k0,
                            k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt, dir[0],
-                           dir[1], kLast ? nullptr : &carry);
+                           dir[1], kLast ? nullptr : &carry, false, kWinCarry);
       // computed before the vote's branch (else the compiler moves the
       // translation behind it, back onto the chain)
       __asm__ volatile("" : "+v"(p.qx), "+v"(p.qy));
@@ -3386,7 +3467,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
         p = p0;
         bd_translate_f(pc, p, i64_to_f32_wide(ax), i64_to_f32_wide(ay), fs, tz, fxe, fye,
                              k0, k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt,
-                             dir[0], dir[1], kLast ? nullptr : &carry);
+                             dir[0], dir[1], kLast ? nullptr : &carry, false, kWinCarry);
       }
     } else {
       // (the throughput kernel: the three-operation carry, advance_adc)
@@ -3401,10 +3482,13 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       dmax2 = __uint_as_float(max(__float_as_uint(dmax2), __float_as_uint(ddx * ddx + ddy * ddy)));
     }
     p.an = an_next;
-    if (kHelper && !kLast && __builtin_amdgcn_readfirstlane(hprog) <= s + 1) {
-      // not published yet (the window's first sub-steps): from the start
-      const uint32_t a = helper_angle_at(s + 1);
-      sincos_turn(a, &dnext[0], &dnext[1]);
+    if (kHelper && kPoll && !kLast) {
+      hseen = __builtin_amdgcn_readfirstlane(hprog);
+      if (hseen <= s + 1) {
+        // not published yet (the window's first sub-steps): from the start
+        const uint32_t a = helper_angle_at(s + 1);
+        sincos_turn(a, &dnext[0], &dnext[1]);
+      }
     }
     if (!kLast) {
       dir[0] = dnext[0];
@@ -3420,7 +3504,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       // sub-step 0 peeled: with reuse_forces it swims with the previous run's
       // actions, and the current ones are loaded once after it (no register
       // holds them across the loop)
-      substep(0, std::false_type{}, pass_t);
+      substep(0, std::false_type{}, pass_t, std::true_type{});
       if (st.reuse && active) {
         fs = st.f_swim[gi];
         tz = st.torque_z[gi];
@@ -3430,16 +3514,29 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
         // registers (no copies) and the scheduler sees across the boundary
         // (E=1 run 53.9 -> 53.4 us).  Not in the in-kernel-noise variant: at
         // its 96-VGPR bound the unrolled loop spills 80 B/lane, not 24.
-        for (s = 1; s + 1 < n_steps - 1; s += 2) {
-          substep(s, std::false_type{}, pass_t);
-          substep(s + 1, std::false_type{}, pass_t);
+        constexpr bool kHelpDoneLoop = kHelper && SWARM_RUN_HELP_DONE;
+        for (s = 1; s + 1 < n_steps - 1 && !(kHelpDoneLoop && hseen == kHelpDone); s += 2) {
+          substep(s, std::false_type{}, pass_t, std::true_type{});
+          substep(s + 1, std::false_type{}, pass_t, std::true_type{});
         }
-        if (s < n_steps - 1) substep(s++, std::false_type{}, pass_t);
+        if constexpr (kHelpDoneLoop) {
+          // the helper has published the whole window: the same sub-steps
+          // without the count's read, its readfirstlane and the branch
+          for (; s + 1 < n_steps - 1; s += 2) {
+            substep(s, std::false_type{}, pass_t, std::false_type{});
+            substep(s + 1, std::false_type{}, pass_t, std::false_type{});
+          }
+        }
+        if (s < n_steps - 1) substep(s++, std::false_type{}, pass_t, std::true_type{});
       } else {
-        for (s = 1; s < n_steps - 1; ++s) substep(s, std::false_type{}, pass_t);
+        for (s = 1; s < n_steps - 1; ++s)
+          substep(s, std::false_type{}, pass_t, std::true_type{});
       }
     }
-    substep(s, std::true_type{}, pass_t);  // velocities of the last sub-step
+    substep(s, std::true_type{}, pass_t, std::true_type{});  // velocities of the last sub-step
+    // the window's image carries (every sub-step above left them alone)
+    if constexpr (SWARM_RUN_WIN_CARRY && kSched >= 3 && !kWalls && decltype(pass_t)::value > 0)
+      redo = !window_carry(p, q0x, q0y, dmax2, d->glim2);
   };
   if (npass == 0)
     run_steps(std::integral_constant<int, 0>{});
@@ -3484,7 +3581,7 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     st.vel[M + gi] = vy;
     st.vel[2 * M + gi] = 0.0f;
     st.omega[gi] = om;
-    window_tail(d, sc, e, i, gi, dmax2);
+    window_tail(d, sc, e, i, gi, dmax2, redo);
     if (st.reuse) {  // the next window's sub-step 0 (the other slot)
       // (fs, tz hold this run's actions unless the window was one sub-step)
       const PrevSlot w = prev_slot(st, par ^ 1);
