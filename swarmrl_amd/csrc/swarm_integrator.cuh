@@ -70,6 +70,24 @@
 #ifndef SWARM_RUN_NOISE_PTR
 #define SWARM_RUN_NOISE_PTR 1
 #endif
+// Round 16, the tail behind the force sums' read-back; each 0 restores the
+// round-15 instruction sequence:
+// the translation's force-free terms (bd_dq_pre) computed in the round trip's
+// latency window, beside the next director
+#ifndef SWARM_RUN_PRE_DQ
+#define SWARM_RUN_PRE_DQ 1
+#endif
+// one wave vote on the speculative conversions per chunk of this many
+// sub-steps, a failed one rolled back and redone on the voting sub-step
+// (run_wave's run_chunks; 0: two votes in every sub-step).  4: same box, E = 1
+// run 35.4 us against 35.7 (24) and 35.9 (10) -- not monotonic in the length,
+// so part of that is how the loop's code happens to be laid out, which a
+// later edit of the sub-step may change: measure again before relying on it
+// (DESIGN.md section 6 "Round 16")
+#ifndef SWARM_RUN_VOTE_CHUNK
+#define SWARM_RUN_VOTE_CHUNK 4
+#endif
+static_assert(SWARM_RUN_VOTE_CHUNK == 0 || SWARM_RUN_VOTE_CHUNK >= 2, "a chunk is 2 sub-steps or more");
 
 namespace swarm {
 
@@ -771,6 +789,25 @@ __device__ __forceinline__ void bd_dq(const PConst& c, float Fx, float Fy, float
   *dqx = f2i32_sat(__builtin_fmaf(*fx, c.mobx, c.sigx * g[0]));
   *dqy = f2i32_sat(__builtin_fmaf(*fy, c.moby, c.sigy * g[1]));
 }
+// The same in two parts, for the latency schedule: the terms that need no
+// pair force (bd_dq_pre, computed while the force sums are in flight) and the
+// force chain (bd_dq_force).  The operations and their roundings are bd_dq's
+// (the product and the sum round apart: no contraction).
+struct DqPre {
+  float c1x, c1y;  // f_ext + f_swim d
+  float sgx, sgy;  // (sig_t / sx) g
+};
+__device__ __forceinline__ DqPre bd_dq_pre(const PConst& c, float fs, float fex, float fey,
+                                           float sn, float cs, const float* g) {
+  return DqPre{fex + fs * cs, fey + fs * sn, c.sigx * g[0], c.sigy * g[1]};
+}
+__device__ __forceinline__ void bd_dq_force(const PConst& c, float Fx, float Fy, const DqPre& t,
+                                            float* fx, float* fy, int32_t* dqx, int32_t* dqy) {
+  *fx = __builtin_fmaf(Fx, 5.9604644775390625e-08f, t.c1x);
+  *fy = __builtin_fmaf(Fy, 5.9604644775390625e-08f, t.c1y);
+  *dqx = f2i32_sat(__builtin_fmaf(*fx, c.mobx, t.sgx));
+  *dqy = f2i32_sat(__builtin_fmaf(*fy, c.moby, t.sgy));
+}
 
 // One Brownian-dynamics sub-step of one particle from its summed WCA force.
 // an_swim: the orientation the swim force points along (p.an, or with
@@ -865,12 +902,18 @@ __device__ __forceinline__ void bd_translate_f(const PConst& c, PState& p, float
                                                uint64_t step, bool last, float* vx, float* vy,
                                                float* w, const float* g, float sn, float cs,
                                                Carry* carry = nullptr, bool adc = false,
-                                               bool no_img = false) {
+                                               bool no_img = false,
+                                               const DqPre* pre = nullptr) {
   const float F[2] = {fx, fy};
   int32_t dqx, dqy;
   // (without noise sigx = sigy = 0: g is finite, so sig g = +-0 changes no
   // displacement)
-  bd_dq(c, F[0], F[1], fs, fex, fey, sn, cs, g, &fx, &fy, &dqx, &dqy);
+  // pre: the force-free terms, computed by the caller ahead of the force
+  // (null or not is a compile-time constant at every call)
+  if (pre)
+    bd_dq_force(c, F[0], F[1], *pre, &fx, &fy, &dqx, &dqy);
+  else
+    bd_dq(c, F[0], F[1], fs, fex, fey, sn, cs, g, &fx, &fy, &dqx, &dqy);
   if (no_img) {  // (a compile-time constant at every call; window_carry)
     p.qx += (uint32_t)dqx;
     p.qy += (uint32_t)dqy;
@@ -3202,11 +3245,26 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
   // sub-steps after it (kPoll = false) neither read the count nor branch on it
   int hseen = 0;
   bool redo = false;  // window_carry: the window's images are not exact
-  auto substep = [&](const int s, auto last_t, auto pass_t, auto poll_t)
+  // Chunked vote (SWARM_RUN_VOTE_CHUNK, run_chunks below): a sub-step with
+  // vote_t false converts speculatively as ever but neither votes nor
+  // branches; it collects per lane what the votes would have tested --
+  // badp: the largest |pair value| seen, as its bit pattern (a NaN's is above
+  // every number's; an unsigned max, so no float max drops a NaN);
+  // bads: the bits in which a force sum's high word differs from its low
+  // word's sign, from psx, psy, the previous sub-step's sums (tested in the
+  // next exchange window, off the chain).
+  uint32_t badp = 0u, bads = 0u;
+  int64_t psx = 0, psy = 0;
+  auto sums_bad = [](int64_t ax, int64_t ay) __attribute__((always_inline)) {
+    return ((uint32_t)(ax >> 32) ^ (uint32_t)((int32_t)ax >> 31)) |
+           ((uint32_t)(ay >> 32) ^ (uint32_t)((int32_t)ay >> 31));
+  };
+  auto substep = [&](const int s, auto last_t, auto pass_t, auto poll_t, auto vote_t)
                      __attribute__((always_inline)) {
     constexpr bool kLast = decltype(last_t)::value;
     constexpr int kPass = decltype(pass_t)::value;  // 0, 1, 2 or 4: up to npass
     constexpr bool kPoll = decltype(poll_t)::value;
+    constexpr bool kVote = decltype(vote_t)::value;
 #ifdef SWARM_PHASE_TIMING
     if (stamp) t0s = t1s = __builtin_amdgcn_s_memtime();
 #endif
@@ -3290,6 +3348,9 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     constexpr bool kDefer = kSched >= 3 && kPass > 0 && !kWalls;
     // ... or not at all: one carry after the window (window_carry)
     constexpr bool kWinCarry = kDefer && SWARM_RUN_WIN_CARRY;
+    // the translation's force-free terms in the round trip's window
+    constexpr bool kPreDq = kDefer && SWARM_RUN_PRE_DQ;
+    DqPre pre = {0.0f, 0.0f, 0.0f, 0.0f};
     float sv_x[2] = {0.0f, 0.0f}, sv_y[2] = {0.0f, 0.0f};
     int sa[2] = {lane, lane}, sb[2] = {lane, lane};
     bool spec_ok = true;
@@ -3317,6 +3378,10 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
               prev_disp();
               if (kDefer && !kWinCarry) apply_carry(p, carry);
             }
+            if (!kVote) {  // the previous sub-step's sums (zero before a chunk's first)
+              bads |= sums_bad(psx, psy);
+              __asm__ volatile("" : "+v"(bads));
+            }
             // pinned here (the compiler would sink them behind the vote branch)
             if (kWinCarry)
               __asm__ volatile("" : "+v"(an_next), "+v"(dmax2));
@@ -3338,8 +3403,9 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
             } else {
               pair_vals(cut2_0, sig6_0, eps24, rx, ry, sv_x[qq], sv_y[qq]);
             }
-            spec_ok = spec_ok && wave_all2(fabsf(sv_x[qq]) < 2147483520.0f,
-                                           fabsf(sv_y[qq]) < 2147483520.0f);
+            if (kVote)  // (else badp, in the round trip's window)
+              spec_ok = spec_ok && wave_all2(fabsf(sv_x[qq]) < 2147483520.0f,
+                                             fabsf(sv_y[qq]) < 2147483520.0f);
             fx = (int64_t)__float2int_rn(sv_x[qq]);
             fy = (int64_t)__float2int_rn(sv_y[qq]);
             sa[qq] = a;
@@ -3403,6 +3469,21 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       __builtin_amdgcn_sched_barrier(0);
       director();
       ext_force();
+      if (kPreDq) {
+        // the translation's force-free terms (after ext_force: kPot's field
+        // force is part of them), pinned here as the director is
+        pre = bd_dq_pre(pc, fs, fxe, fye, dir[0], dir[1], gt);
+        __asm__ volatile("" : "+v"(pre.c1x), "+v"(pre.c1y), "+v"(pre.sgx), "+v"(pre.sgy));
+      }
+      if (kSpec && !kVote) {
+        // what spec_ok votes on, kept per lane: fabsf(v) < 2147483520.0f
+        // fails exactly when v's bits without the sign are 0x4effffff or more
+#pragma unroll
+        for (int qq = 0; qq < (kSpec ? kPass : 0); ++qq)
+          badp = max(badp, max(__float_as_uint(sv_x[qq]) & 0x7fffffffu,
+                               __float_as_uint(sv_y[qq]) & 0x7fffffffu));
+        __asm__ volatile("" : "+v"(badp));
+      }
       if (kHelper && SWARM_HELPER_WIN2) {
         // the round trip's latency window holds no rotation in helper mode:
         // the previous sub-step's displacement and image carries go here
@@ -3456,18 +3537,26 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
       // the image carries: once after the window (kWinCarry), else applied
       // in the next sub-step's exchange window (the last sub-step its own)
       const PState p0 = p;
-      const bool fits = wave_all2(fits_i32(ax), fits_i32(ay));
+      bool fits;
+      if (!kVote) {  // no vote: the sums go to the next sub-step's bads
+        fits = true;
+        psx = ax;
+        psy = ay;
+      } else {
+        fits = wave_all2(fits_i32(ax), fits_i32(ay));
+      }
+      const DqPre* const prep = kPreDq ? &pre : nullptr;
       bd_translate_f(pc, p, (float)(int32_t)ax, (float)(int32_t)ay, fs, tz, fxe, fye, k0,
                            k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt, dir[0],
-                           dir[1], kLast ? nullptr : &carry, false, kWinCarry);
+                           dir[1], kLast ? nullptr : &carry, false, kWinCarry, prep);
       // computed before the vote's branch (else the compiler moves the
       // translation behind it, back onto the chain)
-      __asm__ volatile("" : "+v"(p.qx), "+v"(p.qy));
+      if (kVote) __asm__ volatile("" : "+v"(p.qx), "+v"(p.qy));
       if (__builtin_expect(!fits, 0)) {
         p = p0;
         bd_translate_f(pc, p, i64_to_f32_wide(ax), i64_to_f32_wide(ay), fs, tz, fxe, fye,
                              k0, k1, (uint32_t)i, step0 + (uint64_t)s, kLast, &vx, &vy, &om, gt,
-                             dir[0], dir[1], kLast ? nullptr : &carry, false, kWinCarry);
+                             dir[0], dir[1], kLast ? nullptr : &carry, false, kWinCarry, prep);
       }
     } else {
       // (the throughput kernel: the three-operation carry, advance_adc)
@@ -3498,13 +3587,57 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
     if (stamp) t_bd += __builtin_amdgcn_s_memtime() - t1s;
 #endif
   };
+  // Whole chunks of SWARM_RUN_VOTE_CHUNK sub-steps from s on, none of them the
+  // window's last: each runs without votes and is then voted on once.  A
+  // chunk some lane flags is rolled back and redone by the voting sub-step
+  // (its fix-up pass, its exact re-translation).  The rollback is complete:
+  // a sub-step writes registers and this wave's lacc rows, which every
+  // read-back leaves zeroed whatever was added; positions are any uint32
+  // words; the helper's directors are indexed by sub-step; nothing global is
+  // stored before the window's end.  (poll_t false: only helper mode reads
+  // it, and there chunks begin after kHelpDone.)
+  auto run_chunks = [&](int& s, auto pass_t) __attribute__((always_inline)) {
+    constexpr int kChunkLen = SWARM_RUN_VOTE_CHUNK;
+    for (; s + kChunkLen <= n_steps - 1; s += kChunkLen) {
+      const uint32_t c_qx = p.qx, c_qy = p.qy, c_an = p.an;
+      const float c_dmax2 = dmax2, c_dir0 = dir[0], c_dir1 = dir[1];
+      const float c_g0 = gn[0], c_g1 = gn[1], c_g2 = gn[2];
+      const float* const c_tnext = tnext;
+      badp = 0u;
+      bads = 0u;
+      psx = 0;
+      psy = 0;
+      int k = 0;
+      for (; k + 1 < kChunkLen; k += 2) {
+        substep(s + k, std::false_type{}, pass_t, std::false_type{}, std::false_type{});
+        substep(s + k + 1, std::false_type{}, pass_t, std::false_type{}, std::false_type{});
+      }
+      if (kChunkLen & 1)
+        substep(s + k, std::false_type{}, pass_t, std::false_type{}, std::false_type{});
+      bads |= sums_bad(psx, psy);  // the chunk's last sums
+      if (__builtin_expect(!wave_all(badp < 0x4effffffu && bads == 0u), 0)) {
+        p.qx = c_qx;
+        p.qy = c_qy;
+        p.an = c_an;
+        dmax2 = c_dmax2;
+        dir[0] = c_dir0;
+        dir[1] = c_dir1;
+        gn[0] = c_g0;
+        gn[1] = c_g1;
+        gn[2] = c_g2;
+        tnext = c_tnext;
+        for (k = 0; k < kChunkLen; ++k)
+          substep(s + k, std::false_type{}, pass_t, std::false_type{}, std::true_type{});
+      }
+    }
+  };
   auto run_steps = [&](auto pass_t) __attribute__((always_inline)) {
     int s = 0;
     if (n_steps > 1) {
       // sub-step 0 peeled: with reuse_forces it swims with the previous run's
       // actions, and the current ones are loaded once after it (no register
       // holds them across the loop)
-      substep(0, std::false_type{}, pass_t, std::true_type{});
+      substep(0, std::false_type{}, pass_t, std::true_type{}, std::true_type{});
       if (st.reuse && active) {
         fs = st.f_swim[gi];
         tz = st.torque_z[gi];
@@ -3515,25 +3648,38 @@ __device__ __forceinline__ void run_wave(const Derived* __restrict__ d, const De
         // (E=1 run 53.9 -> 53.4 us).  Not in the in-kernel-noise variant: at
         // its 96-VGPR bound the unrolled loop spills 80 B/lane, not 24.
         constexpr bool kHelpDoneLoop = kHelper && SWARM_RUN_HELP_DONE;
-        for (s = 1; s + 1 < n_steps - 1 && !(kHelpDoneLoop && hseen == kHelpDone); s += 2) {
-          substep(s, std::false_type{}, pass_t, std::true_type{});
-          substep(s + 1, std::false_type{}, pass_t, std::true_type{});
+        // chunked vote: one- and two-pass waves without walls or a potential;
+        // in helper mode once the helper has published the whole window
+        // (a polling sub-step branches on the count anyway)
+        constexpr int kP = decltype(pass_t)::value;
+        constexpr bool kChunk = SWARM_RUN_VOTE_CHUNK > 0 && kSched >= 3 && SWARM_RUN_WIN_CARRY &&
+                                !kWalls && !kPot && (kP == 1 || kP == 2) &&
+                                (!kHelper || kHelpDoneLoop);
+        s = 1;
+        if constexpr (kChunk && !kHelper) run_chunks(s, pass_t);
+        for (; s + 1 < n_steps - 1 && !(kHelpDoneLoop && hseen == kHelpDone); s += 2) {
+          substep(s, std::false_type{}, pass_t, std::true_type{}, std::true_type{});
+          substep(s + 1, std::false_type{}, pass_t, std::true_type{}, std::true_type{});
         }
         if constexpr (kHelpDoneLoop) {
+          if constexpr (kChunk) {
+            if (hseen == kHelpDone) run_chunks(s, pass_t);
+          }
           // the helper has published the whole window: the same sub-steps
           // without the count's read, its readfirstlane and the branch
+          // (with chunks: the sub-steps left over, fewer than a chunk)
           for (; s + 1 < n_steps - 1; s += 2) {
-            substep(s, std::false_type{}, pass_t, std::false_type{});
-            substep(s + 1, std::false_type{}, pass_t, std::false_type{});
+            substep(s, std::false_type{}, pass_t, std::false_type{}, std::true_type{});
+            substep(s + 1, std::false_type{}, pass_t, std::false_type{}, std::true_type{});
           }
         }
-        if (s < n_steps - 1) substep(s++, std::false_type{}, pass_t, std::true_type{});
+        if (s < n_steps - 1) substep(s++, std::false_type{}, pass_t, std::true_type{}, std::true_type{});
       } else {
         for (s = 1; s < n_steps - 1; ++s)
-          substep(s, std::false_type{}, pass_t, std::true_type{});
+          substep(s, std::false_type{}, pass_t, std::true_type{}, std::true_type{});
       }
     }
-    substep(s, std::true_type{}, pass_t, std::true_type{});  // velocities of the last sub-step
+    substep(s, std::true_type{}, pass_t, std::true_type{}, std::true_type{});  // velocities of the last sub-step
     // the window's image carries (every sub-step above left them alone)
     if constexpr (SWARM_RUN_WIN_CARRY && kSched >= 3 && !kWalls && decltype(pass_t)::value > 0)
       redo = !window_carry(p, q0x, q0y, dmax2, d->glim2);
